@@ -1,6 +1,6 @@
 """Benchmark: adversarial-train frames/s of the SECOND KITTI step (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -15,6 +15,14 @@ perturber / sparse layer 0 / head losses; bf16 MFMA sparse layers 1-11 and SECON
 a plain `python bench.py --gpus N` (N > 1) starts torch.distributed.run with N ranks as a child
 process (before this process touches the GPU) and exits with its status. Rank 0 prints ONE JSON
 line; `n_gpus` is the process-group world size.
+
+A plain run sets up, runs W warm-up steps, times K steps (`ms_per_step` = the timed wall time / K, `value` =
+frames / that time) and prints the line. `--dump-outputs DIR` then writes what the last timed step returned and
+the model state it left as DIR/<name>.npy (float32; the frames, the initial weights and so the arrays are the same
+from run to run). `--full` adds, after the timed steps, everything else the line used to carry: the per-kernel
+and per-stage roofline steps (`roofline`, `roofline_kernels`, `stage_roofline`, `step_roofline`,
+`perturber_roofline`), the fp32 `parity_mode` timing and the `cpu_baseline`; `--roofline-kernel`,
+`--no-parity-mode`, `--parity-steps`, `--no-cpu-baseline` and `--cpu-frames` act only under `--full`.
 """
 from __future__ import annotations
 
@@ -40,6 +48,13 @@ def _args():
                     help="strong = StrongAdversarialVoxelNet, sensor_error_bound 0.4 (BASELINE config 5); "
                          "centerpoint = AdversarialCenterPoint nuScenes, batch 4 (BASELINE config 4)")
     ap.add_argument("--fp32", action="store_true", help="dense part in fp32 (parity mode)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (its log values) and the "
+                         "parameters it left as DIR/<name>.npy (float32; rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline timing also run the per-kernel / per-stage roofline steps, the fp32 "
+                         "parity-mode timing and the CPU baseline (the options below narrow it); without --full "
+                         "only the headline is measured")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-frames", type=int, default=2,
                     help="frames per CPU-baseline step (bounded sample: 3 warm-up + 5 timed steps)")
@@ -80,6 +95,40 @@ def _gt(boxes, labels, dev):
     from robustpointclouds_amd.anchor_head import pack_gt
     gb, gl = pack_gt(list(zip(boxes, labels)), dev)
     return dict(gt_boxes=gb, gt_labels=gl)
+
+
+DUMP_BUDGET = 48 << 20   # bytes of array data per --dump-outputs directory (.npy headers come on top)
+
+
+def _snapshot_outputs(log, model):
+    """What the last timed step gave its caller, as named float32 host arrays: the log values train_step returned
+    (log.<key>) and the state it left in the model (param.<name>, and the floating-point buffers — BatchNorm
+    running statistics — as buffer.<name>). Over DUMP_BUDGET in all, every array keeps the same fraction of its
+    elements, drawn with a fixed seed (sorted flat indices), so two builds sample the same positions."""
+    arrs = {}
+    for k, v in (log or {}).items():
+        arrs[f"log.{k}"] = torch.as_tensor(v).detach().float().cpu().numpy().reshape(-1)
+    for n, p in model.named_parameters():
+        arrs[f"param.{n}"] = p.detach().float().cpu().numpy().reshape(-1)
+    for n, b in model.named_buffers():
+        if b.is_floating_point() and b.numel():
+            arrs[f"buffer.{n}"] = b.detach().float().cpu().numpy().reshape(-1)
+    total = sum(x.nbytes for x in arrs.values())
+    if total > DUMP_BUDGET:
+        rng = np.random.default_rng(0)
+        frac = DUMP_BUDGET / total
+        for k in sorted(arrs):
+            x = arrs[k]
+            keep = max(1, int(x.size * frac))
+            if keep < x.size:
+                arrs[k] = x[np.sort(rng.choice(x.size, size=keep, replace=False))]
+    return arrs
+
+
+def _write_outputs(d, arrs):
+    os.makedirs(d, exist_ok=True)
+    for k, x in arrs.items():
+        np.save(os.path.join(d, k + ".npy"), np.ascontiguousarray(x, dtype=np.float32))
 
 
 PEAK = {"fp32_mfma": 157.3, "bf16_mfma": 2500.0}   # TFLOP/s dense, MI355X_MICROARCH.md
@@ -319,79 +368,11 @@ def _parity_mode(a, data, ready, dev, nus, fpf):
     return res
 
 
-def _launch_ranks(n: int) -> int:
-    """Re-run this script under torch.distributed.run with n ranks (child process; no GPU touched
-    here) and return its exit status."""
-    import socket
-    import subprocess
-    import sys
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}",
-           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__), *sys.argv[1:]]
-    return subprocess.run(cmd, env=env).returncode
-
-
-def main():
-    a = _args()
-    import sys
-    if "RANK" not in os.environ and a.gpus > 1:
-        sys.exit(_launch_ranks(a.gpus))
-    from robustpointclouds_amd.trainer import Trainer, init_distributed, make_kitti_model, make_nus_model
-    rank, world, local = init_distributed()
-    if world != a.gpus:
-        print(json.dumps(dict(error=f"--gpus {a.gpus} but the process group has {world} ranks")), flush=True)
-        sys.exit(2)
-    # init_distributed picked the device (local rank modulo the visible GPUs)
-    dev = torch.device("cuda", torch.cuda.current_device())
-    torch.cuda.set_device(dev)
-    torch.manual_seed(0)
-    nus = a.model == "centerpoint"
-    if a.batch is None:
-        a.batch = 4 if nus else 6
-    if nus:
-        model = make_nus_model(device=dev, epoch=3)
-    else:
-        model = make_kitti_model(num_classes=a.classes, device=dev, epoch=3, variant=a.model)
-    tr = Trainer(model, ddp=dist.is_initialized(), bf16=not a.fp32, device=dev)
+def _roofline_steps(a, tr, model, data, ready, timer, sparse_timer, nus):
+    """The --full steps after the timed loop: (kernel-timer summary, sparse per-kernel summary, stage summary,
+    the step's algorithmic FLOPs or None)."""
     from robustpointclouds_amd import dense_bev
-    from robustpointclouds_amd.sparse_encoder import KernelTimer
-    sparse_timer = None
-    if a.roofline_kernel == "dense":
-        timer = dense_bev.ConvTimer()
-        dense_bev.TIMER = timer
-        op = ci = co = None
-        # every sparse conv launch too (forward, data and weight gradients): the roofline entry is the MFMA
-        # kernel with the most time per step across dense and sparse (VERDICT r04 #7: config 4's is sparse)
-        if getattr(model, "middle_encoder", None) is not None:
-            sparse_timer = KernelTimer()
-            model.middle_encoder.timer = sparse_timer
-    else:
-        op, ci, co = a.roofline_kernel.split(",")
-        timer = KernelTimer(op, int(ci), int(co))
-        model.middle_encoder.timer = timer
-    NB = 4
-    data = _nus_batches(NB, a.batch, rank, dev) if nus else _batches(NB, a.batch, rank, dev, a.classes)
-    # the synthetic frames are staged in HBM once: the batch prefetch need not wait for anything to read them
-    ready = torch.cuda.Event()
-    ready.record(torch.cuda.current_stream(dev))
-    # each step queues the next step's hard voxelisation on a side stream (Trainer.train_step
-    # next_points): the timed region still voxelises K batches, one per step. The dense part replays
-    # HIP graphs from the second step on (dense_bev.GRAPHS).
-    for i in range(a.warmup):
-        tr.train_step(*data[i % NB], next_points=data[(i + 1) % NB][0], next_ready=ready)
-    torch.cuda.synchronize()
-    if dist.is_initialized():
-        dist.barrier()
-    t0 = time.perf_counter()
-    for i in range(a.steps):
-        tr.train_step(*data[i % NB], next_points=data[(i + 1) % NB][0], next_ready=ready)
-    torch.cuda.synchronize()
-    if dist.is_initialized():
-        dist.barrier()
-    dt = time.perf_counter() - t0
+    NB = len(data)
     # per-launch HIP-event timing of the roofline kernels: ROCm cannot record timing events inside a captured
     # graph, so 2 more steps of the same workload run with the dense graphs off and the kernel timers on (same
     # kernels, shapes and inputs as the timed steps; rocprof summaries under profiles/ agree); the second of
@@ -431,6 +412,90 @@ def main():
         pert = n_valid * _perturber_flops_per_point(model.adversary) if model.adversary is not None else 0.0
         dense = _dense_flops_per_frame(model, 200, 176) * a.batch
         step_flops = dict(dense=dense, sparse=sparse, perturber=pert, total=dense + sparse + pert)
+    return ks, sks, stages, step_flops
+
+
+def _launch_ranks(n: int) -> int:
+    """Re-run this script under torch.distributed.run with n ranks (child process; no GPU touched
+    here) and return its exit status."""
+    import socket
+    import subprocess
+    import sys
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}",
+           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__), *sys.argv[1:]]
+    return subprocess.run(cmd, env=env).returncode
+
+
+def main():
+    a = _args()
+    import sys
+    if "RANK" not in os.environ and a.gpus > 1:
+        sys.exit(_launch_ranks(a.gpus))
+    from robustpointclouds_amd.trainer import Trainer, init_distributed, make_kitti_model, make_nus_model
+    rank, world, local = init_distributed()
+    if world != a.gpus:
+        print(json.dumps(dict(error=f"--gpus {a.gpus} but the process group has {world} ranks")), flush=True)
+        sys.exit(2)
+    # init_distributed picked the device (local rank modulo the visible GPUs)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    torch.cuda.set_device(dev)
+    torch.manual_seed(0)
+    nus = a.model == "centerpoint"
+    if a.batch is None:
+        a.batch = 4 if nus else 6
+    if nus:
+        model = make_nus_model(device=dev, epoch=3)
+    else:
+        model = make_kitti_model(num_classes=a.classes, device=dev, epoch=3, variant=a.model)
+    tr = Trainer(model, ddp=dist.is_initialized(), bf16=not a.fp32, device=dev)
+    from robustpointclouds_amd import dense_bev
+    from robustpointclouds_amd.sparse_encoder import KernelTimer
+    timer = sparse_timer = None
+    op = ci = co = None
+    if not a.full:      # headline only: no kernel timers installed, no steps after the timed ones
+        pass
+    elif a.roofline_kernel == "dense":
+        timer = dense_bev.ConvTimer()
+        dense_bev.TIMER = timer
+        # every sparse conv launch too (forward, data and weight gradients): the roofline entry is the MFMA
+        # kernel with the most time per step across dense and sparse (VERDICT r04 #7: config 4's is sparse)
+        if getattr(model, "middle_encoder", None) is not None:
+            sparse_timer = KernelTimer()
+            model.middle_encoder.timer = sparse_timer
+    else:
+        op, ci, co = a.roofline_kernel.split(",")
+        timer = KernelTimer(op, int(ci), int(co))
+        model.middle_encoder.timer = timer
+    NB = 4
+    data = _nus_batches(NB, a.batch, rank, dev) if nus else _batches(NB, a.batch, rank, dev, a.classes)
+    # the synthetic frames are staged in HBM once: the batch prefetch need not wait for anything to read them
+    ready = torch.cuda.Event()
+    ready.record(torch.cuda.current_stream(dev))
+    # each step queues the next step's hard voxelisation on a side stream (Trainer.train_step
+    # next_points): the timed region still voxelises K batches, one per step. The dense part replays
+    # HIP graphs from the second step on (dense_bev.GRAPHS).
+    for i in range(a.warmup):
+        tr.train_step(*data[i % NB], next_points=data[(i + 1) % NB][0], next_ready=ready)
+    torch.cuda.synchronize()
+    if dist.is_initialized():
+        dist.barrier()
+    log = None
+    t0 = time.perf_counter()
+    for i in range(a.steps):
+        log = tr.train_step(*data[i % NB], next_points=data[(i + 1) % NB][0], next_ready=ready)
+    torch.cuda.synchronize()
+    if dist.is_initialized():
+        dist.barrier()
+    dt = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:    # before any --full step trains the model further
+        _write_outputs(a.dump_outputs, _snapshot_outputs(log, model))
+    ks, sks, stages, step_flops = {}, {}, {}, None
+    if a.full:
+        ks, sks, stages, step_flops = _roofline_steps(a, tr, model, data, ready, timer, sparse_timer, nus)
     if dist.is_initialized():
         t = torch.tensor([dt], device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -441,7 +506,7 @@ def main():
             else 0.0
     # the reference's precision (fp32) on the same frames, after the headline timing (all ranks take part)
     parity = None
-    if not a.fp32 and not a.no_parity_mode and a.roofline_kernel == "dense":
+    if a.full and not a.fp32 and not a.no_parity_mode and a.roofline_kernel == "dense":
         fpf = step_flops["total"] / a.batch if step_flops is not None else None
         parity = _parity_mode(a, data, ready, dev, nus, fpf)
     frames = world * a.batch * a.steps
@@ -560,7 +625,7 @@ def main():
             res["perturber_roofline"] = _perturber_stages(stages, n_valid, model.adversary, PEAK["fp32_mfma"])
         if parity is not None:
             res["parity_mode"] = parity
-        if not a.no_cpu_baseline and a.model == "voxelnet":
+        if a.full and not a.no_cpu_baseline and a.model == "voxelnet":
             res["cpu_baseline"] = cpu_baseline(a.cpu_frames, a.classes)
         print(json.dumps(res), flush=True)
     if dist.is_initialized():

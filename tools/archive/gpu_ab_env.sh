@@ -6,7 +6,7 @@ OUT=gpurun_out/$1
 VAR=$2
 mkdir -p $OUT
 export TMPDIR=/tmp
-run() { env $VAR=$2 timeout -k 10 200 python -u bench.py --steps 30 --warmup 10 --no-cpu-baseline > $OUT/bench_$1.log 2>&1; }
+run() { env $VAR=$2 timeout -k 10 200 python -u bench.py --full --steps 30 --warmup 10 --no-cpu-baseline > $OUT/bench_$1.log 2>&1; }
 run on1 1 && run off1 0 && run on2 1 && run off2 0
 RC=$?
 for f in on1 off1 on2 off2; do python -c "

@@ -15,7 +15,7 @@ if [ -n "$TESTF" ]; then
   tail -1 $OUT/pytest.log
 fi
 for rep in $(seq 1 $REPS); do for v in $VALS; do
-  env $VAR=$v timeout -k 10 200 python -u bench.py --steps 30 --warmup 10 --no-cpu-baseline > $OUT/bench_${v}_$rep.log 2>&1 || exit 1
+  env $VAR=$v timeout -k 10 200 python -u bench.py --full --steps 30 --warmup 10 --no-cpu-baseline > $OUT/bench_${v}_$rep.log 2>&1 || exit 1
   python -c "
 import json; d=json.loads(open('$OUT/bench_${v}_$rep.log').read().strip().splitlines()[-1]); st=d.get('stage_roofline',{}).get('stages',{})
 print('$VAR=$v', d['value'], d['ms_per_step'], {k: v['avg_ms'] for k, v in st.items()})"

@@ -6,12 +6,12 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 for i in 1 2; do
   for m in 0 2 4; do
-    RPC_SIDE_CUMASK=$m timeout -k 10 200 python -u bench.py --model centerpoint --steps 10 --warmup 4 --no-cpu-baseline --no-parity-mode > $OUT/cp_m${m}_$i.log 2>&1 || exit 1
+    RPC_SIDE_CUMASK=$m timeout -k 10 200 python -u bench.py --full --model centerpoint --steps 10 --warmup 4 --no-cpu-baseline --no-parity-mode > $OUT/cp_m${m}_$i.log 2>&1 || exit 1
   done
 done
 for i in 1 2; do
   for m in 0 2 4; do
-    RPC_SIDE_CUMASK=$m timeout -k 10 200 python -u bench.py --steps 30 --warmup 10 --no-cpu-baseline --no-parity-mode > $OUT/k3_m${m}_$i.log 2>&1 || exit 1
+    RPC_SIDE_CUMASK=$m timeout -k 10 200 python -u bench.py --full --steps 30 --warmup 10 --no-cpu-baseline --no-parity-mode > $OUT/k3_m${m}_$i.log 2>&1 || exit 1
   done
 done
 for f in $OUT/cp_*.log $OUT/k3_*.log; do

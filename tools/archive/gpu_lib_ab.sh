@@ -11,9 +11,9 @@ for rep in 1 2; do
   for lib in "$@"; do
     name=$(basename $lib .so); [ "$lib" = "-" ] && name=intree
     if [ "$lib" = "-" ]; then
-      timeout -k 10 200 python -u bench.py --steps 30 --warmup 10 --no-cpu-baseline > $OUT/bench_${name}_$rep.log 2>&1 || exit 1
+      timeout -k 10 200 python -u bench.py --full --steps 30 --warmup 10 --no-cpu-baseline > $OUT/bench_${name}_$rep.log 2>&1 || exit 1
     else
-      RPC_HIP_LIB=$(realpath $lib) timeout -k 10 200 python -u bench.py --steps 30 --warmup 10 --no-cpu-baseline > $OUT/bench_${name}_$rep.log 2>&1 || exit 1
+      RPC_HIP_LIB=$(realpath $lib) timeout -k 10 200 python -u bench.py --full --steps 30 --warmup 10 --no-cpu-baseline > $OUT/bench_${name}_$rep.log 2>&1 || exit 1
     fi
     python -c "
 import json; d=json.loads(open('$OUT/bench_${name}_$rep.log').read().strip().splitlines()[-1])

@@ -12,8 +12,8 @@ for i in 1 2; do
   RPC_HIP_LIB=$B timeout -k 10 200 python -u tools/pert_bench.py 20000,40000,80000 > $OUT/pb_$i.txt 2>&1 || exit 1
 done
 for i in 1 2 3; do
-  timeout -k 10 200 python -u bench.py --steps 30 --warmup 10 --no-cpu-baseline --no-parity-mode > $OUT/a3_$i.log 2>&1 || exit 1
-  RPC_HIP_LIB=$B timeout -k 10 200 python -u bench.py --steps 30 --warmup 10 --no-cpu-baseline --no-parity-mode > $OUT/b3_$i.log 2>&1 || exit 1
+  timeout -k 10 200 python -u bench.py --full --steps 30 --warmup 10 --no-cpu-baseline --no-parity-mode > $OUT/a3_$i.log 2>&1 || exit 1
+  RPC_HIP_LIB=$B timeout -k 10 200 python -u bench.py --full --steps 30 --warmup 10 --no-cpu-baseline --no-parity-mode > $OUT/b3_$i.log 2>&1 || exit 1
 done
 tail -n 1 $OUT/pytest.log
 for f in $OUT/a3_*.log $OUT/b3_*.log; do

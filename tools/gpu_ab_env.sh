@@ -9,7 +9,7 @@ for rep in $(seq 1 ${REPS:-2}); do
   for e in "$@"; do
     i=$((i+1))
     envs=""; [ "$e" != "-" ] && envs="$e"
-    env $envs timeout -k 10 300 python -u bench.py --steps 30 --warmup 10 --no-parity-mode --no-cpu-baseline \
+    env $envs timeout -k 10 300 python -u bench.py --full --steps 30 --warmup 10 --no-parity-mode --no-cpu-baseline \
       > $OUT/ab_${i}.log 2>&1 || exit $?
     python - "$OUT/ab_${i}.log" "$e" <<'PY'
 import json, sys

@@ -8,8 +8,8 @@ export TMPDIR=/tmp
 B=$PWD/robustpointclouds_amd/_lib/librpc_hip_ab.so
 timeout -k 10 400 python -u -m pytest -x -q --timeout 300 --timeout-method thread tests/test_gpu_centerpoint.py > $OUT/pytest.log 2>&1 || exit 1
 for i in 1 2 3; do
-  timeout -k 10 200 python -u bench.py --model centerpoint --steps 10 --warmup 4 --no-cpu-baseline --no-parity-mode > $OUT/acp_$i.log 2>&1 || exit 1
-  RPC_HIP_LIB=$B timeout -k 10 200 python -u bench.py --model centerpoint --steps 10 --warmup 4 --no-cpu-baseline --no-parity-mode > $OUT/bcp_$i.log 2>&1 || exit 1
+  timeout -k 10 200 python -u bench.py --full --model centerpoint --steps 10 --warmup 4 --no-cpu-baseline --no-parity-mode > $OUT/acp_$i.log 2>&1 || exit 1
+  RPC_HIP_LIB=$B timeout -k 10 200 python -u bench.py --full --model centerpoint --steps 10 --warmup 4 --no-cpu-baseline --no-parity-mode > $OUT/bcp_$i.log 2>&1 || exit 1
 done
 tail -n 1 $OUT/pytest.log
 for f in $OUT/acp_*.log $OUT/bcp_*.log; do
