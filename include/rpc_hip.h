@@ -146,9 +146,15 @@ typedef struct {
                              operands (~2^-16 relative per product); 0 = fp32 MFMA (parity mode) */
   int act16;              /* perf mode: 16-bit activation rows of the hidden layers in the workspace — bit 0:
                              pre-activations z_1..z_3 fp16 (the reference AMP's Linear outputs, train.py:91-103);
-                             bit 1 (with wgrad_split_bf16): gradient rows dh_1..dh_3, dz_1..dz_4 bf16. Applied
-                             when every hidden shape is an encoder-decoder step (width x2 or /2, >= 16), else
-                             fp32 rows; fp32 arithmetic and fp32/double BatchNorm sums either way. 0 = parity */
+                             bit 1: gradient rows dh_1..dh_3, dz_1..dz_4 bf16. Both bits only with
+                             wgrad_split_bf16 (the fp32-MFMA weight gradient reads fp32 rows: without the split
+                             kernel act16 is ignored and every row stays fp32), and only when every hidden shape
+                             is an encoder-decoder step (width x2 or /2, >= 16), else fp32 rows; fp32 arithmetic
+                             and fp32/double BatchNorm sums either way. 0 = parity */
+  int double_sums;         /* parity mode: the BatchNorm batch sums (z, z^2) of the MFMA hidden-layer forward and the
+                             loss statistics (pert, pert^2) accumulated in double — float squares lose the
+                             variance where |mean| >> std (a clamp-saturated feature, a two-point batch). 0 = float
+                             partial sums (perf mode, the previous arithmetic bit for bit) */
 } rpc_perturber_cfg;
 
 size_t rpc_perturber_workspace_size(const rpc_perturber_cfg* cfg, int rows, int slots);

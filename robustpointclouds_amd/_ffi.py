@@ -32,7 +32,7 @@ class PerturberCfg(C.Structure):
     _fields_ = [("F", C.c_int), ("hidden", C.c_int * 3), ("use_attention", C.c_int),
                 ("training", C.c_int), ("sensor_error_bound", C.c_float), ("bn_eps", C.c_float),
                 ("bn_momentum", C.c_float), ("vfe_features", C.c_int), ("wgrad_split_bf16", C.c_int),
-                ("act16", C.c_int)]
+                ("act16", C.c_int), ("double_sums", C.c_int)]
 
 
 class RpcHardVfeCfg(C.Structure):

@@ -62,6 +62,9 @@ def select_engines(model: nn.Module, bf16: bool, pin: bool = False) -> None:
         # takes the perturber backward 0.51 -> 0.435 ms (+0.5 % step) but moves the 6-step adversary update
         # cosine vs fp32 to 0.9949 and act16 = 3 to 0.9940, under tests/test_gpu_bf16_trajectory.py's 0.995
         adv.act16 = int(os.environ.get("RPC_PERT_ACT16", "0")) if bf16 else 0
+        # parity mode accumulates the perturber's batch statistics in double (rpc_perturber_cfg.double_sums); perf
+        # mode keeps the float partial sums
+        adv.double_sums = not bf16
     model.__dict__["_engine_mode"] = bool(bf16)
     if pin:
         model.__dict__["_engine_pinned"] = True

@@ -47,6 +47,7 @@ constexpr int TSTRIDE = 1 + NGRP;
 struct Dev {
   int F, A, C[7];
   int a16;         // effective rpc_perturber_cfg.act16 (0 unless every hidden shape has a 16-bit instantiation)
+  int dsums;       // rpc_perturber_cfg.double_sums: batch sums of z and of the perturbation accumulated in double
   int S;           // channel stride of the SoA activation buffers (>= N)
   int rows, slots, fused, training, use_att, vfe_f;
   float eps, mom;
@@ -180,7 +181,9 @@ __device__ void bn_finalize(Dev& d, int l, double* lds) {
     bn[C + c] = d.be[l][c];
     bn[2 * C + c] = (float)mean;
     bn[3 * C + c] = invstd;
-    double uvar = N > 1 ? var * N / (N - 1) : var;
+    // N < 2 is the fallback (k_xstats): the reference raises before BatchNorm touches its running stats
+    if (N < 2) continue;
+    double uvar = var * N / (N - 1);
     d.rm[l][c] = (1.0f - d.mom) * d.rm[l][c] + d.mom * (float)mean;
     d.rv[l][c] = (1.0f - d.mom) * d.rv[l][c] + d.mom * (float)uvar;
   }
@@ -268,7 +271,9 @@ __global__ __launch_bounds__(BLK) void k_xstats(Dev d) {
   if (threadIdx.x == 0) {
     int N = d.fused ? d.off[d.rows] : d.rows;
     d.meta[0] = N;
-    int flag = (lds[2 * F] != 0.0) || N == 0;
+    // fewer than two points in train mode: the reference's BatchNorm1d raises on one sample and the detector
+    // falls back to the unperturbed voxels with zero losses (adversarial_voxelnet.py:123-132)
+    int flag = (lds[2 * F] != 0.0) || N == 0 || (d.training && N < 2);
     d.meta[1] = flag;
     // s = std(x, unbiased) + 1e-6; any NaN/Inf entry resets the whole vector (:158-163)
     int bad = 0;
@@ -392,7 +397,7 @@ __device__ __forceinline__ float attention(const Dev& d, const float (&xn)[F], f
 }
 
 // output layer: relu(bn4(z4)) -> tanh -> *att -> bounds -> clamp -> out, loss sums
-template <int CI, int F>
+template <int CI, int F, bool EX>
 __global__ __launch_bounds__(BLK) void k_fwd_last(Dev d) {
   __shared__ float sW[F * CI + F + 3 * CI];
   __shared__ double lds[NWAVE * 2 * MAXC];
@@ -416,6 +421,12 @@ __global__ __launch_bounds__(BLK) void k_fwd_last(Dev d) {
     float v[NS];
 #pragma unroll
     for (int k = 0; k < NS; ++k) v[k] = 0.0f;
+    // EX (rpc_perturber_cfg.double_sums): sum pert_f and sum pert_f^2 in double (the square of a float is
+    // exact there, the running sums round at 2^-53). Their difference is the variance, and a feature whose points all sit on the clamp has variance
+    // 0: float sums leave a std of ~3e-4 |pert| there, and the imbalance loss and its gradient with it
+    double pd[EX ? 2 * F : 1];
+#pragma unroll
+    for (int k = 0; k < (EX ? 2 * F : 1); ++k) pd[k] = 0.0;
     if (act) {
       int slot = point_slot(d, i);
       float xv[F], xn[F], h[CI];
@@ -438,15 +449,24 @@ __global__ __launch_bounds__(BLK) void k_fwd_last(Dev d) {
         float p = fminf(fmaxf(pp, -d.bclamp[f]), d.bclamp[f]);
         d.out[(size_t)slot * F + f] = xv[f] + p;
         nrm2 = fmaf(p, p, nrm2);
-        v[2 + f] = p;
-        v[2 + F + f] = p * p;
+        if constexpr (EX) {
+          pd[f] = (double)p;
+          pd[F + f] = (double)p * (double)p;
+        } else {
+          v[2 + f] = p;
+          v[2 + F + f] = p * p;
+        }
         if (f == 3) v[1] = fabsf(p);
       }
       v[0] = sqrtf(nrm2);
       v[2 + 2 * F] = (float)bad;
     }
 #pragma unroll
-    for (int k = 0; k < NS; ++k) acc[k] += (double)wave_sum(v[k]);
+    for (int k = 0; k < NS; ++k)
+      if (!EX || k < 2 || k >= 2 + 2 * F) acc[k] += (double)wave_sum(v[k]);
+    if constexpr (EX)
+#pragma unroll
+      for (int k = 0; k < 2 * F; ++k) acc[2 + k] += wave_sum(pd[k]);
   }
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   if (lane == 0)
@@ -1256,7 +1276,13 @@ __device__ __forceinline__ float grp_sum(float v) {  // sum over the 4 lanes sha
 __device__ __forceinline__ void wave_sums_zero(double* lds) {
   for (int j = threadIdx.x; j < MFW * 2 * MAXC; j += MFBLK) lds[j] = 0.0;
 }
-__device__ __forceinline__ void wave_sums_add(double* lds, int j, float t1, float t2) {
+__device__ __forceinline__ double grp_sum(double v) {
+  v += __shfl_xor(v, 16, 64);
+  v += __shfl_xor(v, 32, 64);
+  return v;
+}
+template <class T>
+__device__ __forceinline__ void wave_sums_add(double* lds, int j, T t1, T t2) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   t1 = grp_sum(t1);
   t2 = grp_sum(t2);
@@ -1434,21 +1460,42 @@ __global__ __launch_bounds__(MFBLK) void k_fwd_mid_mf(Dev d, int l) {
 #pragma unroll
         for (int q = 0; q < TQ; ++q) v[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(hv[s][q], w, v[q], 0, 0, 0);
       }
-      float t1 = 0.0f, t2 = 0.0f;
       ZO* row = zout + (size_t)(16 * j + a) * d.S;
+      fvec<TQ> o[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int nb = n0 + TQ * (4 * g + i);
-        fvec<TQ> o;
 #pragma unroll
-        for (int q = 0; q < TQ; ++q) {
-          o[q] = nb + q < N ? rnd_as<ZO>(v[q][i]) : 0.0f;
-          t1 += o[q];
-          t2 = fmaf(o[q], o[q], t2);
-        }
-        stq<TQ>(row, nb, o);
+        for (int q = 0; q < TQ; ++q) o[i][q] = nb + q < N ? rnd_as<ZO>(v[q][i]) : 0.0f;
+        stq<TQ>(row, nb, o[i]);
       }
-      if (d.training) wave_sums_add(lds, j, t1, t2);
+      if (d.training) {
+        if (d.dsums) {
+          // parity mode: sum z and sum z^2 in double (the square of a float is exact there). The batch variance
+          // is their difference, and float sums lose it where |mean| >> std (6e-8 mean^2 against var + eps:
+          // 0.3 % of the dominant channel's gradient with two points)
+          double t1 = 0.0, t2 = 0.0;
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int q = 0; q < TQ; ++q) {
+              const double od = (double)o[i][q];
+              t1 += od;
+              t2 = fma(od, od, t2);
+            }
+          wave_sums_add(lds, j, t1, t2);
+        } else {
+          float t1 = 0.0f, t2 = 0.0f;
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int q = 0; q < TQ; ++q) {
+              t1 += o[i][q];
+              t2 = fmaf(o[i][q], o[i][q], t2);
+            }
+          wave_sums_add(lds, j, t1, t2);
+        }
+      }
       asm volatile("" ::: "memory");  // keep the next tile's B reads here (register pressure)
     }
   }
@@ -1953,12 +2000,13 @@ static int fill_dev(const rpc_perturber_cfg* cfg, const float* const* P, const f
   d.F = cfg->F;
   d.A = cfg->F / 2 > 1 ? cfg->F / 2 : 1;
   widths(cfg, d.C);
-  // 16-bit rows only where every hidden layer has them, and the bf16 dz rows only with the split-bf16 weight
-  // gradient (the fp32-MFMA k_wgrad_mf reads fp32 rows)
+  // 16-bit rows only where every hidden layer has them, and only with the split-bf16 weight gradient: the
+  // fp32-MFMA k_wgrad_mf reads both its z_{l-1} and its dz_l rows as fp32
   d.a16 = cfg->act16 & 3;
   for (int l = 1; l < 5; ++l)
     if (!a16_shape(d.C[l], d.C[l + 1])) d.a16 = 0;
-  if (!cfg->wgrad_split_bf16) d.a16 &= ~2;
+  if (!cfg->wgrad_split_bf16) d.a16 = 0;
+  d.dsums = cfg->double_sums != 0;
   d.rows = rows;
   d.slots = slots;
   d.S = (int)chan_stride(rows, slots);
@@ -2045,7 +2093,8 @@ static int launch_last(int CI, Dev& d, hipStream_t st, bool bwd) {
 #define CASE(c)                                                                          \
   case c:                                                                                \
     if (bwd) hipLaunchKernelGGL((k_bwd_last_pp<c, F>), dim3((d.S + 63) / 64), dim3(BLK), 0, st, d); \
-    else hipLaunchKernelGGL((k_fwd_last<c, F>), dim3(GRID), dim3(BLK), 0, st, d);        \
+    else if (d.dsums) hipLaunchKernelGGL((k_fwd_last<c, F, true>), dim3(GRID), dim3(BLK), 0, st, d);  \
+    else hipLaunchKernelGGL((k_fwd_last<c, F, false>), dim3(GRID), dim3(BLK), 0, st, d); \
     break;
     RPC_HID(CASE)
 #undef CASE
@@ -2122,8 +2171,8 @@ static int launch_mid(int CI, int CO, Dev& d, int l, hipStream_t st, bool bwd, i
 static bool wgrad_mf_ok(int CO, int CI) {
   return CO % 16 == 0 && CI % 16 == 0 && CO <= MAXC && CI <= MAXC && CO * CI <= 8192;
 }
-// zh16: the jobs' z_{l-1} rows are fp16 (act16 bit 0, layers 2..4); dz rows are bf16 under act16 bit 1 (the
-// split-bf16 kernel only: act16 is a perf-mode option like wgrad_split_bf16)
+// zh16: the jobs' z_{l-1} rows are fp16 (act16 bit 0, layers 2..4); dz rows are bf16 under act16 bit 1. Both only
+// reach the split-bf16 kernel: fill_dev clears d.a16 without it, so k_wgrad_mf always sees fp32 rows
 template <int CO, int CI>
 static void launch_wgrad_mf_t(Dev& d, const MfJobs& M, int njob, bool split, bool zh16, hipStream_t st) {
   if constexpr (CO % 16 == 0 && CI % 16 == 0 && CO <= MAXC && CI <= MAXC && CO * CI <= 8192) {

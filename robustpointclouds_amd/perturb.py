@@ -24,7 +24,11 @@ from . import stage_timer
 
 
 def make_cfg(F, hidden, use_attention, training, sensor_error_bound, bn_eps=1e-3, bn_momentum=0.1,
-             vfe_features=4, wgrad_split_bf16=False, act16=0):
+             vfe_features=4, wgrad_split_bf16=False, act16=0, double_sums=True):
+    """rpc_perturber_cfg (include/rpc_hip.h). act16 (16-bit hidden-layer rows) takes effect only together with
+    wgrad_split_bf16 and on the encoder-decoder shapes it is instantiated for: the fp32-MFMA weight gradient
+    reads fp32 rows, so without the split kernel the library runs the act16 = 0 step, bit for bit. double_sums
+    (parity mode, the default) accumulates the batch statistics in double; the bf16 trainer turns it off."""
     cfg = _ffi.PerturberCfg()
     cfg.F = int(F)
     for k in range(3):
@@ -37,6 +41,7 @@ def make_cfg(F, hidden, use_attention, training, sensor_error_bound, bn_eps=1e-3
     cfg.vfe_features = int(vfe_features)
     cfg.wgrad_split_bf16 = int(bool(wgrad_split_bf16))
     cfg.act16 = int(act16) & 3
+    cfg.double_sums = int(bool(double_sums))
     return cfg
 
 

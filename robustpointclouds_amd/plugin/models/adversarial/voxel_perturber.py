@@ -18,7 +18,9 @@ Declared deviations (SURVEY.md findings 2, §5):
   gradients are unchanged (autograd slices the padded gradients back), and the running
   statistics of the real channels are copied back after each forward;
 * NaN input / NaN perturbations (:150-153, :195-200, :259-262) are detected on the device:
-  the output is the unperturbed input and the loss terms are zeros (no host sync), and
+  the output is the unperturbed input and the loss terms are zeros (no host sync) — likewise a
+  train-mode batch of fewer than two points, where the reference's BatchNorm1d raises and its
+  detector continues unperturbed (adversarial_voxelnet.py:123-132); the running statistics stay — and
   the per-step metrics (:388-409) are accumulated on the device and read only in
   save_l2_norms().
 """
@@ -242,7 +244,8 @@ class VoxelPerturber(nn.Module):
         bn = [m for m in self.model if isinstance(m, nn.BatchNorm1d)][0]
         return _P.make_cfg(F, self._kernel_hidden, self.use_spatial_attention, self.training,
                            self.sensor_error_bound, bn.eps, bn.momentum, vfe_features,
-                           getattr(self, "wgrad_split_bf16", False), getattr(self, "act16", 0))
+                           getattr(self, "wgrad_split_bf16", False), getattr(self, "act16", 0),
+                           getattr(self, "double_sums", True))
 
     def _ensure_width(self, F):
         if F != self.in_features:

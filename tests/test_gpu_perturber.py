@@ -39,6 +39,17 @@ NAMES += ["W5", "b5", "Wa0", "ba0", "Wa1", "ba1"]
 
 @pytest.mark.parametrize("tag", ["car_small", "car_clamp", "3class", "nus"])
 def test_standalone_matches_reference_golden(tag):
+    _standalone_golden(tag, True)
+
+
+@pytest.mark.parametrize("tag", ["car_small", "car_clamp", "3class", "nus"])
+def test_standalone_float_sums_match_reference_golden(tag):
+    """The bf16 trainer's float batch sums (rpc_perturber_cfg.double_sums = 0, what the benchmark runs) against the
+    same golden vectors and the same bounds."""
+    _standalone_golden(tag, False)
+
+
+def _standalone_golden(tag, double_sums):
     d = _load(tag)
     F, hidden = int(d["F"]), [int(h) for h in d["hidden"]]
     dev = torch.device("cuda")
@@ -49,7 +60,7 @@ def test_standalone_matches_reference_golden(tag):
     for l in range(5):
         ps[6 * l + 4].requires_grad_(False)
         ps[6 * l + 5].requires_grad_(False)
-    cfg = P.make_cfg(F, hidden, True, True, 0.2)
+    cfg = P.make_cfg(F, hidden, True, True, 0.2, double_sums=double_sums)
     x = torch.from_numpy(d["x"]).to(dev)
     out, lvec, flags = P.PerturberFn.apply(x, cfg, *ps)
     np.testing.assert_allclose(out.detach().cpu().numpy(), d["out"], rtol=0, atol=TOL)
@@ -78,7 +89,7 @@ def test_standalone_matches_reference_golden(tag):
         np.testing.assert_allclose(ps[6 * l + 4].cpu().numpy(), d[f"rm{l}"], rtol=1e-4, atol=1e-5)
         np.testing.assert_allclose(ps[6 * l + 5].cpu().numpy(), d[f"rv{l}"], rtol=1e-4, atol=1e-5)
     # eval mode with the updated running stats
-    cfg_e = P.make_cfg(F, hidden, True, False, 0.2)
+    cfg_e = P.make_cfg(F, hidden, True, False, 0.2, double_sums=double_sums)
     with torch.no_grad():
         oute, lve, _ = P.PerturberFn.apply(torch.from_numpy(d["x_eval"]).to(dev), cfg_e, *ps)
     np.testing.assert_allclose(oute.cpu().numpy(), d["out_eval"], rtol=0, atol=TOL)
@@ -99,6 +110,16 @@ def _voxels(seed, V, x_pool):
 @pytest.mark.parametrize("tag,V", [("car_small", 3000), ("3class", 1500), ("car_small", 70000), ("nus", 3000)])
 def test_fused_voxels_vfe_matches_oracle(tag, V):
     """nus: F = 5 (x, y, z, intensity, time lag) with HardSimpleVFE(num_features=5), CenterPoint's path."""
+    _fused_vfe(tag, V, True)
+
+
+@pytest.mark.parametrize("tag,V", [("car_small", 3000), ("3class", 1500), ("car_small", 70000), ("nus", 3000)])
+def test_fused_voxels_vfe_float_sums_match_oracle(tag, V):
+    """The bf16 trainer's float batch sums (rpc_perturber_cfg.double_sums = 0) on the fused path, same bounds."""
+    _fused_vfe(tag, V, False)
+
+
+def _fused_vfe(tag, V, double_sums):
     d = _load(tag)
     hidden = [int(h) for h in d["hidden"]]
     F = d["x"].shape[1]
@@ -111,7 +132,7 @@ def test_fused_voxels_vfe_matches_oracle(tag, V):
     for l in range(5):
         ps[6 * l + 4].requires_grad_(False)
         ps[6 * l + 5].requires_grad_(False)
-    cfg = P.make_cfg(F, hidden, True, True, 0.2, vfe_features=F)
+    cfg = P.make_cfg(F, hidden, True, True, 0.2, vfe_features=F, double_sums=double_sums)
     vt, nt = torch.from_numpy(vox).to(dev), torch.from_numpy(npts).to(dev)
     vfe, lvec, pert, flags = P.PerturbVoxelsFn.apply(vt, nt, cfg, *ps)
     op = OraclePerturber(d, F, hidden, dtype=torch.float64)
@@ -276,22 +297,26 @@ def test_wgrad_split_bf16_close_to_fp32():
 
 
 # (gradient rel-L2, cosine) bounds per act16: bf16 gradient rows alone round each term once (unbiased: sums keep
-# ~2^-9 / sqrt(N)); fp16 pre-activations flip ReLU decisions (docstring)
-GRAD_BOUNDS = {2: (1e-2, 0.9999), 3: (0.1, 0.995)}
+# ~2^-9 / sqrt(N)); fp16 pre-activations flip ReLU decisions (docstring). act16 = 1's 16-bit rows are a subset of
+# act16 = 3's (the fp16 z rows without the bf16 gradient rows): it takes act16 = 3's entry
+GRAD_BOUNDS = {1: (0.1, 0.995), 2: (1e-2, 0.9999), 3: (0.1, 0.995)}
 
 
-@pytest.mark.parametrize("act16", [2, 3])
+@pytest.mark.parametrize("act16", [1, 2, 3])
 def test_act16_rows_close_to_fp32(act16):
-    """Perf mode's 16-bit hidden-layer rows (rpc_perturber_cfg.act16: 2 = bf16 gradient rows dh / dz (the bench's
-    default), 3 = also fp16 pre-activations z_1..z_3) against fp32 rows on the same step (metric widths [64, 128, 64], 60k points,
-    split-bf16 weight gradients both ways). The reference AMP (train.py:91-103) runs these Linear layers in fp16.
+    """Perf mode's 16-bit hidden-layer rows (rpc_perturber_cfg.act16: 1 = fp16 pre-activations z_1..z_3, 2 = bf16
+    gradient rows dh / dz, 3 = both; an option, off unless RPC_PERT_ACT16 is set: the bench's default is fp32 rows)
+    against fp32 rows on the same step (metric widths [64, 128, 64], 60k points, split-bf16 weight gradients both ways). The reference AMP (train.py:91-103) runs these Linear layers in fp16.
     Bounds (measured r06 in the test output): perturbation (out - x) and the four loss terms within 5e-3 relative;
     every parameter gradient within GRAD_REL relative L2 and cosine >= GRAD_COS, the biases before train-mode
     BatchNorm excepted (exact gradient 0: summation noise). The gradient bound is loose by construction: with a
     random upstream gradient G the BatchNorm-beta / weight gradients are sums of zero-mean terms (~sqrt(N) of
     N), and every ReLU decision a 16-bit pre-activation takes differently (an fp16 rounding of z ~ 10 is ~5e-3
     of the normalised unit: ~0.2 % of the decisions) moves such a sum by a whole term — the same mechanism as
-    the sparse encoder's (tests/test_gpu_sparse_layers.py). Training-level agreement is bounded by
+    the sparse encoder's (tests/test_gpu_sparse_layers.py). act16 = 1 (fp16 z rows, fp32 gradient rows) takes
+    act16 = 3's bounds, its 16-bit rows being a subset; measured: perturbation 8.5e-4, losses 6.6e-6, worst gradient
+    3.9e-2 relative (cosine 0.99926) — act16 = 3's figures (3.9e-2, 0.99925): the fp16 pre-activations, not the bf16
+    gradient rows, set the gradient error. Training-level agreement is bounded by
     tests/test_gpu_bf16_trajectory.py on the real loss."""
     from robustpointclouds_amd.plugin.models.adversarial.voxel_perturber import VoxelPerturber
     dev = torch.device("cuda")
