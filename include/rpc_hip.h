@@ -716,6 +716,63 @@ int rpc_dcn_backward_f32_ex(const float* x, int xp, const float* off, int offp, 
                             int doff_channels, float* doff_bias, float* dW, int B, int H, int W_, void* workspace,
                             size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ predict: box decoding + NMS
+ * The evaluation-only ops behind `predict`: upstream mmcv `box_iou_rotated` / `nms_rotated`
+ * (mmcv/ops/csrc/pytorch/cuda/nms_rotated_cuda.cu) as reached through mmdet3d `nms_bev` /
+ * `box3d_multiclass_nms` from `Anchor3DHead._predict_by_feat_single`, mmdet3d `circle_nms`
+ * (models/layers/box3d_nms.py) and `CenterPointBBoxCoder.decode` as reached from `CenterHead.predict_by_feat`,
+ * and `DeltaXYZWLHRBBoxCoder.decode`. Batched over groups (frames x classes, frames x tasks): one call, the
+ * per-group counts are read and written on the device.
+ *
+ * A BEV box is (x, y, dx, dy, yaw) fp32. IoU is finite and in [0, 1] for every finite input, 0 when either box
+ * has dx <= 0 or dy <= 0, 1 for identical boxes. */
+int rpc_bev_iou_pairs(const float* a /* [n][5] */, const float* b /* [n][5] */, int n, float* iou /* [n] */,
+                      void* stream);
+
+/* Greedy NMS. boxes [groups][max_n][5] sorted within each group by descending score; counts [groups] device
+ * int32 (clamped to [0, max_n]). keep [groups][max_keep] int32: indices into the group, ascending (= score
+ * order), -1 after the first nkeep[g]; nkeep [groups] device int32. Box j is suppressed by a kept box i < j
+ * when IoU(i, j) > thr (strict). At most max_keep boxes are kept per group. max_n <= RPC_NMS_MAX_N, else
+ * RPC_ERR_UNSUPPORTED (nothing is launched). */
+#define RPC_NMS_MAX_N 4096
+size_t rpc_nms_workspace_size(int groups, int max_n);
+int rpc_nms_bev(const float* boxes, const int* counts, int groups, int max_n, float thr, int max_keep, int* keep,
+                int* nkeep, void* workspace, size_t ws_bytes, void* stream);
+/* The same with centres xy [groups][max_n][2] and the predicate dx*dx + dy*dy <= radius[g] (radius [groups]
+ * device fp32): mmdet3d circle_nms compares the SQUARED distance with the UNSQUARED min_radius, non-strictly. */
+int rpc_nms_circle(const float* xy, const int* counts, const float* radius, int groups, int max_n, int max_keep,
+                   int* keep, int* nkeep, void* workspace, size_t ws_bytes, void* stream);
+
+/* Candidate anchors of the Anchor3DHead maps. cand [batch][ncand] int32: flat anchor indices
+ * ((h * W + w) * S + s) * R + r; anchor_tab: the table of rpc_anchor_head_loss_forward; cls / reg / dir: the
+ * head maps [batch][A*C | A*7 | A*2][H][W] fp32 (A = S*R; dir may be null: label 0) addressed through strides
+ * (host [3][4]: element strides of frame, channel, row, column of cls, reg, dir). Out per candidate: scores [C]
+ * (sigmoid), boxes [7] (DeltaXYZWLHRBBoxCoder.decode), dir_label (argmax of the 2 dir logits; no direction
+ * correction is applied here). */
+int rpc_anchor_decode(const int* cand, int batch, int ncand, int H, int W, int S, int R, int C,
+                      const float* anchor_tab, const float* cls, const float* reg, const float* dir,
+                      const long long* strides, float* scores, float* boxes, int* dir_label, void* stream);
+
+/* Top-K cells of the CenterHead's packed buffers (hm / box as in rpc_center_head_loss_forward). topk
+ * [B][ntasks][K] int32: indices into the task's [ncls][H][W] scores; entries k >= task_k[task] are padding
+ * (valid = 0). Out [B][ntasks][K]: boxes [9] = (x, y, z centre, dim(3), rot = atan2(rot0, rot1), vel(2)) with
+ * x = (col + reg_x) * out_size_factor * voxel_x + pc_x (y likewise with the row) and dim = exp(dim) when
+ * norm_bbox; scores (sigmoid), labels (class within the task), valid = score > score_threshold (when used)
+ * and limit[0:3] <= (x, y, z) <= limit[3:6]. */
+typedef struct {
+  int B, H, W, K;
+  int ntasks;
+  int task_ncls[RPC_CENTER_MAX_TASKS];
+  int task_k[RPC_CENTER_MAX_TASKS];
+  int hm_pitch, box_pitch;
+  int norm_bbox, out_size_factor, use_score_threshold;
+  float voxel_x, voxel_y, pc_x, pc_y;
+  float score_threshold;
+  float limit[6];
+} RpcCenterDecodeCfg;
+int rpc_center_decode(const RpcCenterDecodeCfg* cfg, const float* hm, const float* box, const int* topk,
+                      float* boxes, float* scores, int* labels, int* valid, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

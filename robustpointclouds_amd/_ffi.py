@@ -114,6 +114,17 @@ class RpcCenterCfg(C.Structure):
                 ("hm_pitch", C.c_int), ("box_pitch", C.c_int)]
 
 
+class RpcCenterDecodeCfg(C.Structure):
+    """include/rpc_hip.h RpcCenterDecodeCfg."""
+    _fields_ = [("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("K", C.c_int), ("ntasks", C.c_int),
+                ("task_ncls", C.c_int * 8), ("task_k", C.c_int * 8), ("hm_pitch", C.c_int), ("box_pitch", C.c_int),
+                ("norm_bbox", C.c_int), ("out_size_factor", C.c_int), ("use_score_threshold", C.c_int),
+                ("voxel_x", C.c_float), ("voxel_y", C.c_float), ("pc_x", C.c_float), ("pc_y", C.c_float),
+                ("score_threshold", C.c_float), ("limit", C.c_float * 6)]
+
+
+NMS_MAX_N = 4096   # include/rpc_hip.h RPC_NMS_MAX_N
+
 # name -> (restype, argtypes); every symbol here must be exported by the .so
 SIGNATURES = {
     "rpc_version": (C.c_char_p, []),
@@ -232,6 +243,13 @@ SIGNATURES = {
     "rpc_anchor_head_loss_forward": (i32, [C.POINTER(RpcHeadCfg), vp, vp, vp, i32, vp, vp, vp, vp, vp, sz, vp]),
     "rpc_anchor_head_loss_backward": (i32, [C.POINTER(RpcHeadCfg), vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp,
                                             sz, vp]),
+    "rpc_bev_iou_pairs": (i32, [vp, vp, i32, vp, vp]),
+    "rpc_nms_workspace_size": (sz, [i32, i32]),
+    "rpc_nms_bev": (i32, [vp, vp, i32, i32, C.c_float, i32, vp, vp, vp, sz, vp]),
+    "rpc_nms_circle": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, sz, vp]),
+    "rpc_anchor_decode": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, C.POINTER(C.c_longlong), vp,
+                                vp, vp, vp]),
+    "rpc_center_decode": (i32, [C.POINTER(RpcCenterDecodeCfg), vp, vp, vp, vp, vp, vp, vp, vp]),
 }
 
 

@@ -457,6 +457,70 @@ class Anchor3DHead(nn.Module):
         z, lay, _ = self._z(feat, w)
         return self.loss_from_z(z, b, lay, gb, gl)
 
+    # ------------------------------------------------------------------ detections
+    @torch.no_grad()
+    def predict_by_feat(self, cls_scores, bbox_preds, dir_cls_preds, cfg=None):
+        """Detections from the head maps (one level; each a tensor [B, A*C | A*7 | A*2, H, W] or a one-element
+        list): upstream `_predict_by_feat_single` + `box3d_multiclass_nms`, restated and batched. Per frame the
+        `nms_pre` anchors of the largest max-class score are decoded; per class the candidates above `score_thr`
+        go through rotated NMS at `nms_thr` in score order (a box may survive under several classes); the
+        classes are concatenated (class-major, by score within a class) and cut to the `max_num` best scores;
+        the direction bin corrects the yaw of the survivors. All frames x classes are ONE rpc_nms_bev call
+        (postprocess.py); the only device -> host transfer is of the final per-frame counts.
+        -> per frame dict(bboxes_3d [n, 7], scores_3d [n], labels_3d [n] int64)."""
+        from . import postprocess as pp
+        one = lambda v: v[0] if isinstance(v, (list, tuple)) else v
+        cls, reg, dcl = one(cls_scores), one(bbox_preds), one(dir_cls_preds)
+        cfg = dict(self.test_cfg or {}) if cfg is None else dict(cfg)
+        if not cfg.get("use_rotate_nms", True):
+            raise NotImplementedError("test_cfg.use_rotate_nms=False (axis-aligned BEV NMS) is not built")
+        B, _, H, W = cls.shape
+        C_, A = self.num_classes, self.num_anchors
+        g = self.prior_generator
+        S, R = len(g.ranges), len(g.rotations)
+        N = H * W * A
+        dev = cls.device
+        key = (H, W, str(dev))
+        if key not in self._tab_cache:
+            self._tab_cache[key] = anchor_table(g, H, W).to(dev)
+        nms_pre = int(cfg.get("nms_pre", -1))
+        if 0 < nms_pre < N:
+            best = torch.sigmoid(cls.float().reshape(B, A, C_, H, W).amax(2)).permute(0, 2, 3, 1).reshape(B, N)
+            cand = best.topk(nms_pre, dim=1)[1]
+        else:
+            cand = torch.arange(N, device=dev)[None].expand(B, N)
+        K = cand.shape[1]
+        scores, boxes, dirl = pp.anchor_decode(cand, cls, reg, dcl, self._tab_cache[key], S, R, C_)
+        # groups = frames x classes: each class's candidates in score order at the front of its group
+        sc = scores.permute(0, 2, 1)                                            # [B, C, K]
+        cand_ok = sc > float(cfg.get("score_thr", 0.0))
+        order = torch.sort(sc.masked_fill(~cand_ok, -1.0), dim=2, descending=True, stable=True)[1]
+        counts = cand_ok.sum(2)
+        bev = torch.cat([boxes[..., 0:2], boxes[..., 3:5], boxes[..., 6:7]], -1)   # x, y, dx, dy, yaw
+        bev = bev[:, None].expand(B, C_, K, 5).gather(2, order[..., None].expand(-1, -1, -1, 5))
+        keep, nkeep = pp.nms_bev_batched(bev.reshape(B * C_, K, 5), counts.reshape(-1), float(cfg["nms_thr"]))
+        keep, nkeep = keep.view(B, C_, K).long(), nkeep.view(B, C_, 1)
+        kept = torch.arange(K, device=dev)[None, None] < nkeep
+        src = order.gather(2, keep.clamp(min=0))                                # candidate of each kept slot
+        ksc = sc.gather(2, src).masked_fill(~kept, -1.0).reshape(B, C_ * K)
+        kept, src = kept.reshape(B, C_ * K), src.reshape(B, C_ * K)
+        total = kept.sum(1)
+        max_num = int(cfg.get("max_num", C_ * K))
+        M = min(max_num, C_ * K)
+        by_class = pp.compact_front(kept)[0]
+        by_score = torch.sort(ksc, dim=1, descending=True, stable=True)[1]
+        sel = torch.where((total > max_num)[:, None], by_score, by_class)[:, :M]
+        src = src.gather(1, sel)
+        out_b = boxes.gather(1, src[..., None].expand(-1, -1, 7)).clone()
+        out_s = ksc.gather(1, sel)
+        out_l = sel // K
+        if self.use_direction_classifier and dcl is not None:
+            rot = limit_period(out_b[..., 6] - self.dir_offset, self.dir_limit_offset, math.pi)
+            out_b[..., 6] = rot + self.dir_offset + math.pi * dirl.gather(1, src).to(out_b.dtype)
+        n = total.clamp(max=M).tolist()                                         # the one device -> host transfer
+        return [dict(bboxes_3d=out_b[b, :n[b]], scores_3d=out_s[b, :n[b]], labels_3d=out_l[b, :n[b]])
+                for b in range(B)]
+
 
 def pack_gt(samples, device):
     """GT of one batch -> padded (boxes [B, M, 7] fp32, labels [B, M] int64, -1 padding). `samples`:

@@ -672,6 +672,67 @@ class CenterHead(nn.Module):
         out.packed = lv
         return out
 
+    @torch.no_grad()
+    def predict_by_feat(self, preds_dicts, cfg=None):
+        """Detections from the packed head buffers (`_packed` of forward's dicts): upstream
+        `CenterHead.predict_by_feat` with nms_type="circle", restated and batched. Per task: sigmoid heatmap,
+        the global top `max_per_img` of the task's C*H*W scores (= upstream's per-class then cross-class top-K
+        for K <= H*W), CenterPointBBoxCoder.decode (rpc_center_decode), the boxes outside
+        `post_center_limit_range` or not above `score_threshold` dropped, circle NMS at `min_radius[task]` in
+        score order, the first `post_max_size` kept. Per frame the tasks are concatenated in order, labels
+        offset by the earlier tasks' class counts, z moved from the box centre to the bottom centre. All frames
+        x tasks are ONE rpc_nms_circle call; the only device -> host transfer is of the final per-frame counts.
+        -> per frame dict(bboxes_3d [n, 9], scores_3d [n], labels_3d [n] int64)."""
+        from . import postprocess as pp
+        cfg = dict(self.test_cfg or {}) if cfg is None else dict(cfg)
+        nms_type = cfg.get("nms_type", "circle")
+        if isinstance(nms_type, (list, tuple)):
+            nms_type = nms_type[0] if len(set(nms_type)) == 1 else tuple(nms_type)
+        if nms_type != "circle":
+            raise NotImplementedError(f"test_cfg.nms_type={nms_type!r} is not built (only 'circle')")
+        hm, box, B, H, W = preds_dicts[0][0]["_packed"]
+        dev = hm.device
+        ncls = self.num_classes
+        T = len(ncls)
+        K = int(cfg["max_per_img"])
+        task_k = [min(K, n * H * W) for n in ncls]
+        K = max(task_k)
+        hm4 = hm.view(B, H, W, -1)
+        topk = torch.zeros((B, T, K), dtype=torch.long, device=dev)
+        c0 = 0
+        for t, n in enumerate(ncls):
+            heat = torch.sigmoid(hm4[..., c0:c0 + n].float()).permute(0, 3, 1, 2).reshape(B, -1)
+            topk[:, t, :task_k[t]] = heat.topk(task_k[t], dim=1)[1]
+            c0 += n
+        osf = cfg.get("out_size_factor", self.train_cfg["out_size_factor"])
+        vs = cfg.get("voxel_size", self.train_cfg["voxel_size"])
+        boxes, scores, labels, valid = pp.center_decode(
+            hm, box, topk, ncls, task_k, B, H, W, self.norm_bbox, osf, vs, self.train_cfg["point_cloud_range"],
+            cfg.get("score_threshold"), cfg["post_center_limit_range"])
+        # groups = frames x tasks: the valid boxes (still in score order) at the front of each group
+        order, counts = pp.compact_front(valid)
+        xy = boxes[..., :2].gather(2, order[..., None].expand(-1, -1, -1, 2))
+        ck = (str(dev), B, tuple(float(r) for r in cfg["min_radius"][:T]))
+        if getattr(self, "_post_consts", (None,))[0] != ck:   # per-group radii, per-task label offsets: uploaded once
+            self._post_consts = (ck, torch.tensor(ck[2] * B, dtype=torch.float32, device=dev),
+                                 torch.tensor([sum(ncls[:t]) for t in range(T)], dtype=torch.long, device=dev))
+        _, radius, offs = self._post_consts
+        post = min(int(cfg.get("post_max_size", K)), K)
+        keep, nkeep = pp.nms_circle_batched(xy.reshape(B * T, K, 2), counts.reshape(-1), radius, post)
+        keep, nkeep = keep.view(B, T, post).long(), nkeep.view(B, T, 1)
+        kept = (torch.arange(post, device=dev)[None, None] < nkeep).reshape(B, T * post)
+        src = order.gather(2, keep.clamp(min=0))                                # top-K slot of each kept box
+        flat = (src + torch.arange(T, device=dev)[None, :, None] * K).reshape(B, T * post)
+        sel, total = pp.compact_front(kept)
+        flat = flat.gather(1, sel)
+        out_b = boxes.reshape(B, T * K, 9).gather(1, flat[..., None].expand(-1, -1, 9)).clone()
+        out_b[..., 2] = out_b[..., 2] - out_b[..., 5] * 0.5
+        out_l = (labels + offs[None, :, None]).reshape(B, T * K).gather(1, flat)
+        out_s = scores.reshape(B, T * K).gather(1, flat)
+        n = total.tolist()                                                      # the one device -> host transfer
+        return [dict(bboxes_3d=out_b[b, :n[b]], scores_3d=out_s[b, :n[b]], labels_3d=out_l[b, :n[b]])
+                for b in range(B)]
+
     def loss(self, feats, batch_data_samples, **kwargs):
         preds = self(feats)
         if isinstance(batch_data_samples, dict):

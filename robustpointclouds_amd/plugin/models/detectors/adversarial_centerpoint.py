@@ -122,15 +122,17 @@ class AdversarialCenterPoint(CenterPoint):
 
     @torch.no_grad()
     def predict(self, batch_inputs_dict, batch_data_samples=None, **kwargs) -> List[dict]:
-        """Raw per-task head outputs (CenterPoint box decoding / circle NMS are evaluation-only, out of
-        this build's scope) plus the perturbation norm like :262-273."""
+        """Detections per frame — dict(bboxes_3d [n, 9], scores_3d, labels_3d) — from
+        `pts_bbox_head.predict_by_feat` (CenterPoint box decoding + circle NMS on the HIP kernels of
+        csrc/postprocess.hip) plus the perturbation norm like :262-273."""
         vd = dict(batch_inputs_dict["voxels"])
         vd.setdefault("batch_size", batch_inputs_dict.get("batch_size"))
         preds = self.pts_bbox_head(self.extract_pts_feat(vd))
-        res = [{k: v for k, v in p[0].items() if not k.startswith("_")} for p in preds]
+        res = self.pts_bbox_head.predict_by_feat(preds)
         if self._current_l2_norm is not None:
+            l2 = float(self._current_l2_norm)
             for r in res:
-                r["perturbation_l2_norm"] = float(self._current_l2_norm)
+                r["perturbation_l2_norm"] = l2
         return res
 
     def set_epoch(self, epoch):

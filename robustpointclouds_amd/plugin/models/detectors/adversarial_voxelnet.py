@@ -114,28 +114,16 @@ class AdversarialVoxelNet(VoxelNet):
 
     @torch.no_grad()
     def predict(self, batch_inputs_dict: Dict[str, Tensor], batch_data_samples=None, **kwargs) -> List[dict]:
-        """Decoded top-scoring boxes per frame (score_thr / nms_pre of test_cfg); rotated NMS
-        is evaluation-only and out of this build's scope."""
+        """Detections per frame — dict(bboxes_3d [n, 7], scores_3d, labels_3d) — from
+        `bbox_head.predict_by_feat`: box decoding, per-class rotated NMS and the direction-bin correction of
+        upstream Anchor3DHead, on the HIP kernels of csrc/postprocess.hip; plus the perturbation norm when the
+        adversary ran."""
         x = self.extract_feat(batch_inputs_dict)
-        cls, reg, dcl = self.bbox_head(x)
-        cls, reg = cls[0], reg[0]
-        B, _, H, W = cls.shape
-        head = self.bbox_head
-        anchors = head.anchors((H, W), cls.device).reshape(-1, 7)
-        tc = self.test_cfg or {}
-        out = []
-        for b in range(B):
-            s = torch.sigmoid(cls[b].permute(1, 2, 0).reshape(-1, head.num_classes))
-            d = reg[b].permute(1, 2, 0).reshape(-1, 7)
-            sc, lab = s.max(dim=1)
-            k = min(int(tc.get("nms_pre", 100)), sc.numel())
-            top = sc.topk(k).indices
-            boxes = head.bbox_coder.decode(anchors[top], d[top])
-            keep = sc[top] > float(tc.get("score_thr", 0.1))
-            res = dict(bboxes_3d=boxes[keep], scores_3d=sc[top][keep], labels_3d=lab[top][keep])
-            if self._current_l2_norm is not None:
-                res["perturbation_l2_norm"] = float(self._current_l2_norm)
-            out.append(res)
+        out = self.bbox_head.predict_by_feat(*self.bbox_head(x))
+        if self._current_l2_norm is not None:
+            l2 = float(self._current_l2_norm)
+            for res in out:
+                res["perturbation_l2_norm"] = l2
         return out
 
     @property

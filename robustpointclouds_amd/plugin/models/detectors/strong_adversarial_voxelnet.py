@@ -211,6 +211,12 @@ class StrongAdversarialVoxelNet(VoxelNet):
 
     @torch.no_grad()
     def predict(self, batch_inputs_dict, batch_data_samples=None, **kwargs):
+        """Detections per frame from `bbox_head.predict_by_feat` (see AdversarialVoxelNet.predict)."""
         x = self.extract_feat(batch_inputs_dict, batch_data_samples)
-        return self.bbox_head(x)
+        out = self.bbox_head.predict_by_feat(*self.bbox_head(x))
+        l2 = batch_inputs_dict.get("adversarial_l2_norm")   # set by extract_feat when the adversary ran
+        if l2 is not None:
+            for res in out:
+                res["perturbation_l2_norm"] = float(l2)
+        return out
 
