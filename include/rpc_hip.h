@@ -290,6 +290,32 @@ int rpc_spconv_gemm_bf16_n(const void* a, int n_src, int kg, const int* map, int
 int rpc_spconv_gemm_h16(const void* a, int fmt, int n_src, int kg, const int* map, int kvol, int rev, int n_out,
                         const void* bt, int ng, float* out, const float* prev_z, const float* prev_bn, float* part,
                         int epi, void* stream);
+/* Eval mode (SparseEncoder under model.eval()): BatchNorm with the running statistics, nothing reduced over the
+ * batch's rows, no statistics updated.
+ * rpc_bn_fold_batch: up to 32 layers in one launch; per layer, in fp32,
+ *   invstd = 1 / sqrtf(running_var + eps), scale = gamma * invstd, shift = fmaf(-running_mean, scale, beta);
+ *   bn [4c] = scale, beta, running_mean, invstd (the vector of rpc_spconv_forward's in_bn, rpc_sparse_res_forward,
+ *   rpc_to_h16_rows and rpc_sparse_to_dense, which compute (z - mean) * scale + beta), fold [2c] = scale, shift.
+ *   Either output may be NULL. */
+typedef struct {
+  const float* gamma;
+  const float* beta;
+  const float* running_mean;
+  const float* running_var;
+  float eps;
+  int c;
+  float* bn;     /* [4c] or NULL */
+  float* fold;   /* [2c] or NULL */
+} RpcBnFold;
+int rpc_bn_fold_batch(const RpcBnFold* descs, int n, void* stream);
+/* rpc_spconv_gemm_h16_infer: rpc_spconv_gemm_h16's forward GEMM (operands a, bt in fmt) whose epilogue computes
+ *   y = fmaxf(fmaf(acc, scale[c], shift[c]) + (res ? res[row][c] : 0), 0)        (fold = scale, shift [2 * ng])
+ * and stores the next layer's operand rows out_h16 [n_out][round8(ng)] in fmt (padding columns zero) and, when
+ * out_f32 is not NULL, the fp32 rows [n_out][ng] (a later block identity). The accumulator is not stored; no
+ * BatchNorm partial sums. res: fp32 rows [n_out][ng] or NULL. */
+int rpc_spconv_gemm_h16_infer(const void* a, int fmt, int n_src, int kg, const int* map, int kvol, int n_out,
+                              const void* bt, int ng, const float* fold, const float* res, void* out_h16,
+                              float* out_f32, void* stream);
 /* the same GEMM with the BatchNorm finalize of its partial sums fused in (the last
  * arriving blocks sum the partial rows in two fixed-order levels and apply rpc_bn_finalize's arithmetic),
  * replacing the rpc_bn_finalize launch that followed it: epi 0 -> mode 0 (this layer's bn + running stats),

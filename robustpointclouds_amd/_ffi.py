@@ -85,6 +85,13 @@ class RpcSpconvWprep(C.Structure):
                 ("dgrad", C.c_int), ("fmt", C.c_int)]
 
 
+class RpcBnFold(C.Structure):
+    """include/rpc_hip.h RpcBnFold."""
+    _fields_ = [("gamma", C.c_void_p), ("beta", C.c_void_p), ("running_mean", C.c_void_p),
+                ("running_var", C.c_void_p), ("eps", C.c_float), ("c", C.c_int), ("bn", C.c_void_p),
+                ("fold", C.c_void_p)]
+
+
 class RpcSparseLayer(C.Structure):
     """include/rpc_hip.h RpcSparseLayer (one sparse conv of the rpc_sparse_backward layer table)."""
     _fields_ = [("kind", C.c_int), ("ci", C.c_int), ("co", C.c_int), ("kvol", C.c_int), ("n_in", C.c_int),
@@ -164,6 +171,8 @@ SIGNATURES = {
     "rpc_spconv_gemm_bf16": (i32, [vp, i32, vp, i32, i32, i32, vp, i32, vp, vp, vp, vp, i32, vp]),
     "rpc_spconv_gemm_bf16_n": (i32, [vp, i32, i32, vp, i32, i32, i32, vp, i32, vp, vp, vp, vp, i32, vp]),
     "rpc_spconv_gemm_h16": (i32, [vp, i32, i32, i32, vp, i32, i32, i32, vp, i32, vp, vp, vp, vp, i32, vp]),
+    "rpc_bn_fold_batch": (i32, [vp, i32, vp]),
+    "rpc_spconv_gemm_h16_infer": (i32, [vp, i32, i32, i32, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp]),
     "rpc_to_h16_rows": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     "rpc_spconv_wgrad_h16": (i32, [vp, i32, i32, vp, i32, i32, vp, i32, vp, vp, sz, vp]),
     "rpc_sparse_res_forward_h16": (i32, [vp, vp, vp, i32, i32, vp, vp, i32, vp, vp]),

@@ -91,7 +91,9 @@ __device__ __forceinline__ f32x4 mfma16(uint4 a, uint4 b, f32x4 c) {
 
 // E_RES: the data gradient into a basicblock's output rows: m = (acc + g2) * [out > 0] with the BatchNorm-
 // backward partial sums (sum m, sum m * xhat(z)) of that layer — rpc_sparse_res_backward fused into the GEMM
-enum { E_FWD = 0, E_DGRAD = 1, E_PLAIN = 2, E_RES = 3 };
+// E_INFER: the eval-mode forward: y = relu(acc * scale + shift (+ res)) with the folded running statistics, stored
+// as the next layer's 16-bit operand rows (and optionally fp32 rows); no z, no BatchNorm partial sums
+enum { E_FWD = 0, E_DGRAD = 1, E_PLAIN = 2, E_RES = 3, E_INFER = 4 };
 
 struct GB {
   const u16* a;       // gathered source rows [Nsrc][CP] bf16
@@ -106,9 +108,12 @@ struct GB {
   const float* ebn;   // E_DGRAD: scale, beta, mean, invstd [4*CO_real]
   float* part;        // [blocks][2*NGP] or null
   RpcBnFin fin;       // BatchNorm finalize by the last-arriving blocks (fin.ticket null: off)
-  int fmt;            // operand format of a and bt: 0 bf16, 1 fp16 (E_FWD only)
+  int fmt;            // operand format of a and bt: 0 bf16, 1 fp16 (E_FWD and E_INFER only)
   const float* eg2;   // E_RES: the other gradient contribution [Nout][CO_real] (identity path) or null
   const float* eout;  // E_RES: the block output rows [Nout][CO_real] (ReLU mask)
+  // E_INFER: out = fp32 rows [Nout][CO_real] or null, ebn = scale, shift [2*CO_real], eg2 = the block identity
+  // rows [Nout][CO_real] or null, fmt = format of a, bt and oh
+  u16* oh;            // E_INFER: operand rows [Nout][round8(CO_real)] (padding columns zero)
 };
 
 // ---- BatchNorm finalize fused into the GEMM (RpcBnFin, data gradients): the partial rows every block writes
@@ -187,7 +192,7 @@ __global__ __launch_bounds__(64 * gw_of(KGP, NT), gemm_waves_per_simd(KGP, NT)) 
   constexpr int BV = NGP * KGH / 8;           // 16-B vectors per step's weight tile
   constexpr int BPT = (BV + GBLK - 1) / GBLK;
   __shared__ __attribute__((aligned(16))) u16 sB[2][NGP * LS];
-  __shared__ int sN[GBM * MAXK];
+  __shared__ __attribute__((aligned(16))) int sN[GBM * MAXK];
   __shared__ unsigned wmask[GW];
   __shared__ int klist[MAXK];
   __shared__ int nk;
@@ -353,6 +358,73 @@ __global__ __launch_bounds__(64 * gw_of(KGP, NT), gemm_waves_per_simd(KGP, NT)) 
       const int r = r0 + w * WR + rt * 16 + (lane >> 4) * 4 + j;
       prow[rt][j] = r < g.Nout ? r : -1;
     }
+  if constexpr (EPI == E_INFER) {
+    // Eval-mode epilogue. The accumulator layout gives a lane one column of four rows: stored as it is, a 16-bit
+    // row element would be a 2-byte store at the row pitch. Each wave passes its 16 x (16 * TG) tile through
+    // LDS instead — its own rows of the neighbour table, which only this wave ever reads or writes and which is
+    // dead after the loop — and reads it back row-major: a lane stores 4 * TG consecutive columns (8 or 16 B),
+    // four lanes one 32 * TG-byte row segment. scale / shift of the block's columns sit in the weight tiles' space
+    // (free after the loop's last barrier), as E_DGRAD's parameters do.
+    constexpr int TG = NT >= 2 ? 2 : 1, CW = 16 * TG, SP = CW + 8, VW = CW / 4;   // SP: 8 mod 16 elements
+    static_assert(NT % TG == 0, "tile groups");
+    static_assert(16 * SP * 2 <= WR * MAXK * 4 && (WR * MAXK * 4) % 16 == 0, "per-wave staging in sN");
+    static_assert(2 * NGP * 4 <= (int)sizeof(sB), "scale / shift in sB");
+    const int C = g.CO_real, OP = (C + 7) / 8 * 8;
+    float* const sSS = (float*)&sB[0][0];   // [2][NGP]: scale, shift
+    for (int j = tid; j < 2 * NGP; j += GBLK) {
+      const int q = j / NGP, c = j - q * NGP;
+      sSS[j] = g.ebn[q * C + min(c, C - 1)];
+    }
+    __syncthreads();
+    u16* const stg = (u16*)(sN + w * WR * MAXK);
+    const int cl = lane & 15, rg = lane >> 4;        // accumulator layout: column, row group
+    const int orow = lane >> 2, oc = (lane & 3) * VW;  // store layout: row of the tile, first column of the group
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+#pragma unroll
+      for (int n0 = 0; n0 < NT; n0 += TG) {
+        float rr[TG][4];
+#pragma unroll
+        for (int t = 0; t < TG; ++t) {
+          const int cc = min((n0 + t) * 16 + cl, C - 1);
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            rr[t][j] = g.eg2 ? g.eg2[(long long)max(prow[rt][j], 0) * C + cc] : 0.0f;
+        }
+#pragma unroll
+        for (int t = 0; t < TG; ++t) {
+          const int col = (n0 + t) * 16 + cl;
+          const float sc = sSS[col], sh = sSS[NGP + col];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const int row = prow[rt][j];
+            float y = 0.0f;
+            if (row >= 0 && col < C) {
+              y = fmaxf(fmaf(acc[rt][n0 + t][j], sc, sh) + rr[t][j], 0.0f);
+              if (g.out) g.out[(long long)row * C + col] = y;
+            }
+            stg[(rg * 4 + j) * SP + t * 16 + cl] = to_h16<F16 ? 1 : 0>(y);
+          }
+        }
+        // the wave's LDS accesses execute in order: only the compiler has to keep them so
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const int row = r0 + w * WR + rt * 16 + orow, c0 = n0 * 16 + oc;
+        if constexpr (TG == 2) {
+          const uint4 v = *(const uint4*)&stg[orow * SP + oc];
+          if (row < g.Nout && c0 < OP) *(uint4*)&g.oh[(long long)row * OP + c0] = v;
+        } else {
+          const uint2 v = *(const uint2*)&stg[orow * SP + oc];
+          if (row < g.Nout && c0 < OP) *(uint2*)&g.oh[(long long)row * OP + c0] = v;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      }
+    }
+    return;
+  }
   // E_DGRAD / E_RES: the BatchNorm parameters of the block's columns are staged in LDS (the weight tiles' space, free
   // after the loop's last barrier), and with few output tiles every tile's z rows are loaded before the first store
   // (one round trip for the epilogue instead of one per tile: the stores of tile n may alias the loads of tile n + 1
@@ -904,7 +976,10 @@ template <int KGP, int NT>
 static void launch_k(int epi, const GB& a, int n_rows, hipStream_t st) {
   constexpr int RT = rt_of(KGP, NT), GW = gw_of(KGP, NT), GBM = 16 * RT * GW;
   const int nblk = (n_rows + GBM - 1) / GBM;
-  if (a.fmt == 1)   // fp16 operands: forward GEMMs only (checked by gemm_bf16_launch)
+  if (epi == E_INFER) {
+    if (a.fmt == 1) hipLaunchKernelGGL((k_gemm_bf16<KGP, NT, E_INFER, true>), dim3(nblk), dim3(64 * GW), 0, st, a);
+    else hipLaunchKernelGGL((k_gemm_bf16<KGP, NT, E_INFER>), dim3(nblk), dim3(64 * GW), 0, st, a);
+  } else if (a.fmt == 1)   // fp16 operands: forward GEMMs only (checked by gemm_bf16_launch)
     hipLaunchKernelGGL((k_gemm_bf16<KGP, NT, E_FWD, true>), dim3(nblk), dim3(64 * GW), 0, st, a);
   else if (epi == E_FWD) hipLaunchKernelGGL((k_gemm_bf16<KGP, NT, E_FWD>), dim3(nblk), dim3(64 * GW), 0, st, a);
   else if (epi == E_DGRAD) hipLaunchKernelGGL((k_gemm_bf16<KGP, NT, E_DGRAD>), dim3(nblk), dim3(64 * GW), 0, st, a);
@@ -1021,7 +1096,7 @@ static int gemm_bf16_launch(GB& g, const void* a, int n_src, int kg, const int* 
   // 32-bit buffer offsets (src * CP + c) * 2 into the gathered source table of n_src rows
   if (n_src >= 0 && (long long)n_src * r8(kg) * 2 >= (1LL << 31)) return RPC_ERR_UNSUPPORTED;
   if (n_out == 0) return RPC_OK;
-  if (g.fmt != 0 && (g.fmt != 1 || epi != E_FWD)) return RPC_ERR_UNSUPPORTED;
+  if (g.fmt != 0 && (g.fmt != 1 || (epi != E_FWD && epi != E_INFER))) return RPC_ERR_UNSUPPORTED;
   g.a = (const u16*)a;
   g.CP = r8(kg);
   g.nbr = map;
@@ -1080,6 +1155,72 @@ extern "C" int rpc_spconv_gemm_res(const void* a, int n_src, int kg, const int* 
   g.eg2 = g2;
   g.eout = out;
   return gemm_bf16_launch(g, a, n_src, kg, map, kvol, rev, n_out, bt, ng, m, z, bn, part, E_RES, stream);
+}
+
+// The eval-mode forward of one 16-bit layer in one launch: the gathered GEMM of rpc_spconv_gemm_h16 (epi 0) with
+// y = relu(acc * scale + shift (+ res)) as its epilogue (fold: scale, shift [2 * ng] of rpc_bn_fold_batch) -> the
+// next layer's operand rows out_h16 [n_out][round8(ng)] in fmt, and fp32 rows out_f32 [n_out][ng] when given
+extern "C" int rpc_spconv_gemm_h16_infer(const void* a, int fmt, int n_src, int kg, const int* map, int kvol,
+                                         int n_out, const void* bt, int ng, const float* fold, const float* res,
+                                         void* out_h16, float* out_f32, void* stream) {
+  if (n_out < 0 || n_src < 0 || (fmt != 0 && fmt != 1)) return RPC_ERR_ARG;
+  if (n_out == 0) return RPC_OK;
+  if (!a || !map || !bt || !fold || !out_h16) return RPC_ERR_ARG;
+  GB g;
+  memset(&g, 0, sizeof(g));
+  g.fmt = fmt;
+  g.eg2 = res;
+  g.oh = (u16*)out_h16;
+  return gemm_bf16_launch(g, a, n_src, kg, map, kvol, 0, n_out, bt, ng, out_f32, nullptr, fold, nullptr, E_INFER,
+                          stream);
+}
+
+// Eval mode: the running statistics of up to 32 BatchNorm layers folded in one launch (blockIdx.y = layer) into
+// bn [4c] = scale, beta, mean, invstd — the vector every kernel that applies (z - mean) * scale + beta takes — and
+// fold [2c] = scale, shift = beta - mean * scale, the epilogue form of rpc_spconv_gemm_h16_infer
+namespace rpc {
+namespace spb {
+constexpr int BNFOLD_MAX = 32;
+struct BnFoldBatch {
+  RpcBnFold d[BNFOLD_MAX];
+};
+__global__ __launch_bounds__(BLK) void k_bn_fold_batch(BnFoldBatch b) {
+  const RpcBnFold& d = b.d[blockIdx.y];
+  const int c = blockIdx.x * BLK + threadIdx.x, C = d.c;
+  if (c >= C) return;
+  const float mean = d.running_mean[c];
+  const float invstd = 1.0f / sqrtf(d.running_var[c] + d.eps);
+  const float scale = d.gamma[c] * invstd;
+  const float shift = fmaf(-mean, scale, d.beta[c]);
+  if (d.bn) {
+    d.bn[c] = scale;
+    d.bn[C + c] = d.beta[c];
+    d.bn[2 * C + c] = mean;
+    d.bn[3 * C + c] = invstd;
+  }
+  if (d.fold) {
+    d.fold[c] = scale;
+    d.fold[C + c] = shift;
+  }
+}
+}  // namespace spb
+}  // namespace rpc
+
+extern "C" int rpc_bn_fold_batch(const RpcBnFold* descs, int n, void* stream) {
+  if (n < 0 || n > BNFOLD_MAX || (n > 0 && !descs)) return RPC_ERR_ARG;
+  if (n == 0) return RPC_OK;
+  BnFoldBatch b;
+  memset(&b, 0, sizeof(b));
+  int most = 0;
+  for (int i = 0; i < n; ++i) {
+    const RpcBnFold& d = descs[i];
+    if (!d.gamma || !d.beta || !d.running_mean || !d.running_var || d.c < 1 || (!d.bn && !d.fold)) return RPC_ERR_ARG;
+    b.d[i] = d;
+    most = d.c > most ? d.c : most;
+  }
+  hipLaunchKernelGGL(k_bn_fold_batch, dim3(cdiv(most, BLK), n), dim3(BLK), 0, (hipStream_t)stream, b);
+  RPC_LAUNCH_CHECK();
+  return RPC_OK;
 }
 
 // largest block of the GEMM launches (rows): fin_groups of n_out at the smallest block (64 rows)

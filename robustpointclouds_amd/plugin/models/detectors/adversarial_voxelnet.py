@@ -13,9 +13,13 @@ encoder takes the reference's explicit compaction path. loss (:153-427) is
 robustpointclouds_amd.adversarial_loss.combine_adversarial_losses — the same values with the
 `.item()` branches moved onto the device. Debug prints (:98-109, :193-196, :306-365) and the
 every-100-iterations manual backward (:325-338) are not reproduced.
+
+`attack_eval()` is the attacked evaluation of evaluate_kitti_adversarial_attack.py:23-62: inside the block the gate
+also opens in eval mode, and the perturber runs its eval forward.
 """
 from __future__ import annotations
 
+from contextlib import contextmanager
 from typing import Dict, List, Optional
 
 import torch
@@ -56,12 +60,34 @@ class AdversarialVoxelNet(VoxelNet):
         self._adv_iter = 0
         self._loss_debug_iter = 0
         self._adversarial_disabled = False
+        self._attack_eval = False
         self._last_flags = None
         self._last_perturbed_voxels = None
 
     def _gate(self):
+        if getattr(self, "_attack_eval", False):
+            # attacked evaluation (attack_eval below): the gate as the reference's evaluator sees it after
+            # forcing the detector's own `training` on and `_adversarial_disabled` off
+            return self.adversary is not None and self._epoch >= 3
         return (self.adversary is not None and self.training and
                 not getattr(self, "_adversarial_disabled", False) and self._epoch >= 3)
+
+    @contextmanager
+    def attack_eval(self):
+        """Attacked evaluation — what evaluate_kitti_adversarial_attack.py:23-62 adds to the stock test loop:
+        inside the block the perturber runs although the detector is in eval mode (adversary present and
+        `_epoch >= 3`; `_adversarial_disabled` is ignored, :37-38). The reference forces only the detector's
+        own `training` attribute, so every submodule — the perturber included — stays in eval mode: the
+        perturber takes its eval forward (running-statistics BatchNorm, eval bounds,
+        voxel_perturber.py:214-231, 339-344), which `self.adversary.training == False` already selects here.
+        No module's `training` changes; the previous `_attack_eval` is restored when the block exits, also
+        when it raises."""
+        prev = getattr(self, "_attack_eval", False)
+        self._attack_eval = True
+        try:
+            yield self
+        finally:
+            self._attack_eval = prev
 
     def extract_feat(self, batch_inputs_dict: dict):
         vd = batch_inputs_dict["voxels"]

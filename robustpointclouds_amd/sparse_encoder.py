@@ -14,6 +14,11 @@ statistics in their epilogues and normalisation+ReLU folded into the next conv's
 backward walks the layers in reverse (dense gather, BN backward folded into the dgrad
 gather, weight grads as split-K slabs). State-dict keys follow mmdet3d's module names;
 conv weights are stored [K, C_in, C_out] (k = (kz*3 + ky)*3 + kx).
+
+Under eval() the forward normalises with the running statistics instead (_eval_forward): nothing is reduced over
+the batch, no statistic is written, and the 16-bit engine runs one GEMM launch per layer with BatchNorm, the
+block identity, ReLU and the next layer's operand rows in its epilogue (rpc_spconv_gemm_h16_infer). There is no
+backward through it.
 """
 from __future__ import annotations
 
@@ -298,6 +303,11 @@ class SparseEncoder(nn.Module):
             self._grids[key] = g
         return g
 
+    def train(self, mode: bool = True):
+        if mode:
+            self.__dict__.pop("_eval_tiles", None)   # training changes the weights the eval-mode tiles were cut from
+        return super().train(mode)
+
     def forward(self, voxel_features, coors, batch_size):
         params = []
         for m in self.layers():
@@ -531,6 +541,198 @@ class _RulebookPlan:
         return self.plan[li]
 
 
+def _scatter_dense(lib, enc, last, B, dev, st):
+    """relu(bn(z)) of the last layer (`last`: its spec, z, bn, coors_out, n_out) scattered into the module's
+    persistent dense BEV image; returns (dense, flags, (C, D, H, W))."""
+    D, H, Wd = enc.shapes[-1]
+    C = last["spec"].co
+    flags = (1 if enc.dense_nhwc else 0) | (2 if enc.dense_bf16 else 0)
+    dt = torch.bfloat16 if enc.dense_bf16 else torch.float32
+    # the dense BEV lives in one persistent buffer per module (re-zeroed each step): the SECOND
+    # forward graph (dense_bev._graph_run) then reads it in place instead of from a copy
+    # one buffer per shape: a returning shape (full batches after a partial last one) reuses the
+    # storage its graph captured, and a dropped encoder frees them all
+    # (at most the two most recent shapes are kept — e.g. full batches and a partial last one, or the
+    # two engines' dtypes; a captured graph that still holds an evicted buffer keeps it alive itself and
+    # copies from the new one when its shape returns)
+    # Cleared where the previous step scattered (rpc_sparse_dense_clear on the coordinates it kept) rather
+    # than zero-filled whole: 6 x 256 x 200 x 176 bf16 = 108 MB per step for SECOND against the ~10^4
+    # occupied cells' bytes.
+    bkey = (B, H, Wd, C * D, dt, enc.dense_nhwc, dev)
+    bufs = enc.__dict__.setdefault("_dense_bufs", {})
+    ent = bufs.pop(bkey, None)
+    shp = _ffi.int_arr((B, D, H, Wd))
+    if ent is None:
+        while len(bufs) >= 2:
+            bufs.pop(next(iter(bufs)))
+        base = torch.empty((B, H, Wd, C * D) if enc.dense_nhwc else (B, C * D, H, Wd), dtype=dt, device=dev)
+        dense_bev.mark_stable(base)
+        base.zero_()
+    else:
+        base, prev_coors, prev_n = ent
+        _ffi.check(lib.rpc_sparse_dense_clear(_ffi.ptr(prev_coors), prev_n, C, shp, flags, _ffi.ptr(base), st),
+                   "rpc_sparse_dense_clear")
+        # (the coordinates may come from a rulebook side stream: not reusable before this clear has run)
+        prev_coors.record_stream(torch.cuda.current_stream(dev))
+    # the coordinates kept for the next clear must be this step's own: a submanifold last layer's output
+    # coordinates are its input's (possibly the caller's tensor, which it may refill in place) — keep a copy
+    keep = last["coors_out"].clone() if last["spec"].kind == "subm" else last["coors_out"]
+    bufs[bkey] = (base, keep, last["n_out"])      # most recently used last
+    if enc.dense_nhwc:   # channels_last image, logically [B, C*D, H, W]
+        dense = base.permute(0, 3, 1, 2)
+    else:
+        dense = base.view(base.shape)
+    _ffi.check(lib.rpc_sparse_to_dense(_ffi.ptr(last["z"]), _ffi.ptr(last["bn"]), _ffi.ptr(last["coors_out"]),
+                                       last["n_out"], C, shp, flags, _ffi.ptr(dense), st), "rpc_sparse_to_dense")
+    return dense, flags, (C, D, H, Wd)
+
+
+def _eval_fold(lib, mods, dev, st):
+    """Eval mode: every layer's running statistics folded in one launch (rpc_bn_fold_batch; 32 layers per launch)
+    -> per layer (bn [4c] = scale, beta, mean, invstd, the vector the row / gather / dense kernels take;
+    fold [2c] = scale, shift, the epilogue form of rpc_spconv_gemm_h16_infer)."""
+    cs = [m[1].num_features for m in mods]
+    sl = [(6 * c + 3) // 4 * 4 for c in cs]     # 16-byte aligned vectors (the row passes read them as float4)
+    flat = torch.empty(sum(sl), dtype=torch.float32, device=dev)
+    out, off = [], 0
+    for c, n in zip(cs, sl):
+        out.append((flat[off:off + 4 * c], flat[off + 4 * c:off + 6 * c]))
+        off += n
+    for g0 in range(0, len(mods), 32):
+        group = mods[g0:g0 + 32]
+        descs = (_ffi.RpcBnFold * len(group))()
+        for i, m in enumerate(group):
+            b = m[1]
+            bn, fold = out[g0 + i]
+            descs[i] = _ffi.RpcBnFold(b.weight.data_ptr(), b.bias.data_ptr(), b.running_mean.data_ptr(),
+                                      b.running_var.data_ptr(), float(b.eps), cs[g0 + i], bn.data_ptr(),
+                                      fold.data_ptr())
+        _ffi.check(lib.rpc_bn_fold_batch(descs, len(group), st), "rpc_bn_fold_batch")
+    return out
+
+
+def _eval_tiles(lib, enc, mods, dev, st, fmt):
+    """Eval mode: the forward weight tiles of the 16-bit layers (1..) in format fmt. The weights are constant
+    while the module evaluates, so the tiles are kept on the module, keyed by device, format and every weight's
+    storage and `_version`; train() drops them (SparseEncoder.train: an optimizer that writes through raw
+    pointers does not move `_version`)."""
+    Ws = [m[0].weight for m in mods]
+    key = (str(dev), int(fmt), tuple((w.data_ptr(), w._version, w.dtype) for w in Ws))
+    ent = enc.__dict__.get("_eval_tiles")
+    if ent is not None and ent[0] == key:
+        return ent[1]
+    jobs = []
+    for li in range(1, len(enc.specs)):
+        sp = enc.specs[li]
+        W = Ws[li].detach().float().contiguous()
+        bt = torch.empty(lib.rpc_spconv_bf16_weight_elems(sp.K, sp.ci, sp.co, 0), dtype=torch.bfloat16, device=dev)
+        jobs.append((li, sp, W, bt))
+    for g0 in range(0, len(jobs), 32):
+        group = jobs[g0:g0 + 32]
+        descs = (_ffi.RpcSpconvWprep * len(group))()
+        for i, (li, sp, W, bt) in enumerate(group):
+            descs[i] = _ffi.RpcSpconvWprep(W.data_ptr(), bt.data_ptr(), sp.K, sp.ci, sp.co, 0, int(fmt))
+        _ffi.check(lib.rpc_spconv_prep_weight_bf16_batch(descs, len(group), st), "rpc_spconv_prep_weight_bf16_batch")
+    tiles = {li: bt for li, sp, W, bt in jobs}
+    enc.__dict__["_eval_tiles"] = (key, tiles)
+    return tiles
+
+
+def _eval_forward(lib, enc, feats, coors, B, params, mods, dev, st, tm_stage, e_stage):
+    """SparseEncoderFn.forward under eval(): BatchNorm with the running statistics. Nothing is reduced over the
+    batch's rows, no statistic or counter is written, nothing is kept for a backward.
+    fp32 engine: the training kernels with the folded vectors and no partial sums. 16-bit engine: layer 0 in
+    fp32 + its 16-bit rows as in training; layers 1 .. L-2 one rpc_spconv_gemm_h16_infer launch each (BatchNorm,
+    block identity, ReLU and the next layer's operand rows in the GEMM's epilogue; fp32 rows only where a later
+    block reads them as its identity); the last layer a plain GEMM into z, normalised by the dense scatter.
+    Rulebooks, the dense image and the timers are the training path's."""
+    specs = enc.specs
+    nl = len(specs)
+    bf16 = enc.bf16
+    fmt = FWD_FMT if bf16 else 0
+    folded = _eval_fold(lib, mods, dev, st)
+    tiles = _eval_tiles(lib, enc, mods, dev, st, fmt) if bf16 else {}
+    plan = enc.__dict__.get("_prepared", {}).pop((coors.data_ptr(), feats.shape[0], B), None)
+    if plan is None or plan.main != torch.cuda.current_stream(dev):
+        plan = _RulebookPlan(lib, enc, coors, feats.shape[0], B, dev)
+    else:
+        enc.__dict__.pop("_coors_ready", None)
+    main = torch.cuda.current_stream(dev)
+    idents = {sp.res for sp in specs if sp.res >= 0}   # layers whose fp32 output rows a later block adds
+    src, src_bn, hsrc = feats, None, None
+    outs = {}
+    L = []
+    for li, sp in enumerate(specs):
+        W = params[3 * li]
+        bn, fold = folded[li]
+        p = plan.get(li)
+        main.wait_event(p["ev"])
+        n_out = p["n_out"]
+        rec = dict(spec=sp, n_in=p["n_in"], n_out=n_out, nbr=p["nbr"], coors_out=p["coors_out"], bn=bn)
+        L.append(rec)
+        last = li == nl - 1
+        h16 = bf16 and li > 0
+        tm = enc.timer is not None and enc.timer.wants("fwd", sp)
+        e0 = enc.timer.start() if tm else None
+        if h16 and not last:
+            # conv + BatchNorm (+ identity) + ReLU + operand rows in one launch
+            oh = torch.empty((n_out, _r8(sp.co)), dtype=torch.bfloat16, device=dev)
+            of = torch.empty((n_out, sp.co), dtype=torch.float32, device=dev) if li in idents else None
+            res = outs[sp.res] if sp.res >= 0 else None
+            _ffi.check(lib.rpc_spconv_gemm_h16_infer(_ffi.ptr(hsrc), fmt, hsrc.shape[0], sp.ci, _ffi.ptr(p["nbr"]),
+                                                     sp.K, n_out, _ffi.ptr(tiles[li]), sp.co, _ffi.ptr(fold),
+                                                     _ffi.ptr(res), _ffi.ptr(oh), _ffi.ptr(of), st),
+                       "rpc_spconv_gemm_h16_infer")
+            if tm:
+                enc.timer.stop(e0, p["nbr"], sp.ci, sp.co, f"rpc::spb::k_gemm_bf16<{_r32(sp.ci)}, {_r16(sp.co) // 16}, 4>",
+                               "bf16")
+            if of is not None:
+                outs[li] = of
+            hsrc = oh
+            continue
+        z = torch.empty((n_out, sp.co), dtype=torch.float32, device=dev)
+        if h16:
+            _ffi.check(lib.rpc_spconv_gemm_h16(_ffi.ptr(hsrc), fmt, hsrc.shape[0], sp.ci, _ffi.ptr(p["nbr"]), sp.K, 0,
+                                               n_out, _ffi.ptr(tiles[li]), sp.co, _ffi.ptr(z), None, None, None, 0, st),
+                       "rpc_spconv_gemm_h16")
+        else:
+            _ffi.check(lib.rpc_spconv_forward(_ffi.ptr(src), _ffi.ptr(src_bn), sp.ci, _ffi.ptr(p["nbr"]), sp.K, n_out,
+                                              _ffi.ptr(W), sp.co, _ffi.ptr(z), None, st), "rpc_spconv_forward")
+        if tm:
+            kn = (f"rpc::spb::k_gemm_bf16<{_r32(sp.ci)}, {_r16(sp.co) // 16}, 0>" if h16 else
+                  f"rpc::sp::k_gemm<{sp.ci}, {sp.co}, {1 if li else 0}, 0>")
+            enc.timer.stop(e0, p["nbr"], sp.ci, sp.co, kn, "bf16" if h16 else "fp32")
+        rec["z"] = z
+        if last:
+            break
+        if sp.mat:
+            out = torch.empty((n_out, sp.co), dtype=torch.float32, device=dev)
+            ob = torch.empty((n_out, _r8(sp.co)), dtype=torch.bfloat16, device=dev) if bf16 else None
+            res = outs[sp.res] if sp.res >= 0 else None
+            if bf16:
+                _ffi.check(lib.rpc_sparse_res_forward_h16(_ffi.ptr(z), _ffi.ptr(bn), _ffi.ptr(res), n_out, sp.co,
+                                                          _ffi.ptr(out), _ffi.ptr(ob), fmt, None, st),
+                           "rpc_sparse_res_forward_h16")
+            else:
+                _ffi.check(lib.rpc_sparse_res_forward(_ffi.ptr(z), _ffi.ptr(bn), _ffi.ptr(res), n_out, sp.co,
+                                                      _ffi.ptr(out), None, st), "rpc_sparse_res_forward")
+            outs[li] = out
+            src, src_bn, hsrc = out, None, ob
+        else:
+            src, src_bn = z, bn
+            if bf16:
+                hsrc = torch.empty((n_out, _r8(sp.co)), dtype=torch.bfloat16, device=dev)
+                _ffi.check(lib.rpc_to_h16_rows(_ffi.ptr(z), _ffi.ptr(bn), n_out, sp.co, 1, fmt, _ffi.ptr(hsrc), None,
+                                               st), "rpc_to_h16_rows")
+    dense, flags, _ = _scatter_dense(lib, enc, L[-1], B, dev, st)
+    if enc.flop_probe is not None:
+        enc.flop_probe.append([(rec["nbr"], rec["spec"].ci, rec["spec"].co) for rec in L])
+    if tm_stage:
+        stage_timer.TIMER.stop("sparse_fwd", e_stage, _sparse_bytes(L, bf16, dense.numel() * dense.element_size(),
+                                                                      backward=False))
+    return dense
+
+
 class SparseEncoderFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feats, coors, enc: SparseEncoder, B: int, *params):
@@ -542,6 +744,9 @@ class SparseEncoderFn(torch.autograd.Function):
         feats = feats.contiguous().float()
         coors = coors.to(torch.int32).contiguous()
         mods = enc.layers()
+        ctx.eval_mode = not enc.training
+        if ctx.eval_mode:
+            return _eval_forward(lib, enc, feats, coors, B, params, mods, dev, st, tm_stage, e_stage)
         src, src_bn = feats, None
         # perf mode: layers >= 1 gather bf16 rows of relu(bn(z)) (O(1) values); layer 0 stays fp32 —
         # its input is the raw VFE mean (coordinates up to 70 m, where a bf16 step is 0.5 m)
@@ -627,47 +832,7 @@ class SparseEncoderFn(torch.autograd.Function):
                     _ffi.check(lib.rpc_to_h16_rows(_ffi.ptr(z), _ffi.ptr(bn), n_out, sp.co, 1, fmt, _ffi.ptr(hsrc),
                                                    _ffi.ptr(hwg) if fmt else None, st), "rpc_to_h16_rows")
         _ffi.bump_batches([m[1] for m in mods])
-        last = L[-1]
-        D, H, Wd = enc.shapes[-1]
-        C = last["spec"].co
-        flags = (1 if enc.dense_nhwc else 0) | (2 if enc.dense_bf16 else 0)
-        dt = torch.bfloat16 if enc.dense_bf16 else torch.float32
-        # the dense BEV lives in one persistent buffer per module (re-zeroed each step): the SECOND
-        # forward graph (dense_bev._graph_run) then reads it in place instead of from a copy
-        # one buffer per shape: a returning shape (full batches after a partial last one) reuses the
-        # storage its graph captured, and a dropped encoder frees them all
-        # (at most the two most recent shapes are kept — e.g. full batches and a partial last one, or the
-        # two engines' dtypes; a captured graph that still holds an evicted buffer keeps it alive itself and
-        # copies from the new one when its shape returns)
-        # Cleared where the previous step scattered (rpc_sparse_dense_clear on the coordinates it kept) rather
-        # than zero-filled whole: 6 x 256 x 200 x 176 bf16 = 108 MB per step for SECOND against the ~10^4
-        # occupied cells' bytes.
-        bkey = (B, H, Wd, C * D, dt, enc.dense_nhwc, dev)
-        bufs = enc.__dict__.setdefault("_dense_bufs", {})
-        ent = bufs.pop(bkey, None)
-        shp = _ffi.int_arr((B, D, H, Wd))
-        if ent is None:
-            while len(bufs) >= 2:
-                bufs.pop(next(iter(bufs)))
-            base = torch.empty((B, H, Wd, C * D) if enc.dense_nhwc else (B, C * D, H, Wd), dtype=dt, device=dev)
-            dense_bev.mark_stable(base)
-            base.zero_()
-        else:
-            base, prev_coors, prev_n = ent
-            _ffi.check(lib.rpc_sparse_dense_clear(_ffi.ptr(prev_coors), prev_n, C, shp, flags, _ffi.ptr(base), st),
-                       "rpc_sparse_dense_clear")
-            # (the coordinates may come from a rulebook side stream: not reusable before this clear has run)
-            prev_coors.record_stream(torch.cuda.current_stream(dev))
-        # the coordinates kept for the next clear must be this step's own: a submanifold last layer's output
-        # coordinates are its input's (possibly the caller's tensor, which it may refill in place) — keep a copy
-        keep = last["coors_out"].clone() if last["spec"].kind == "subm" else last["coors_out"]
-        bufs[bkey] = (base, keep, last["n_out"])      # most recently used last
-        if enc.dense_nhwc:   # channels_last image, logically [B, C*D, H, W]
-            dense = base.permute(0, 3, 1, 2)
-        else:
-            dense = base.view(base.shape)
-        _ffi.check(lib.rpc_sparse_to_dense(_ffi.ptr(last["z"]), _ffi.ptr(last["bn"]), _ffi.ptr(last["coors_out"]),
-                                           last["n_out"], C, shp, flags, _ffi.ptr(dense), st), "rpc_sparse_to_dense")
+        dense, flags, (C, D, H, Wd) = _scatter_dense(lib, enc, L[-1], B, dev, st)
         if enc.flop_probe is not None:
             enc.flop_probe.append([(rec["nbr"], rec["spec"].ci, rec["spec"].co) for rec in L])
         if tm_stage:
@@ -684,6 +849,9 @@ class SparseEncoderFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gdense):
+        if ctx.eval_mode:
+            raise RuntimeError("SparseEncoder: backward through an eval-mode forward is not built (running-statistics "
+                               "BatchNorm keeps nothing for it); call train() for gradients")
         enc = ctx.enc
         timed = enc.timer is not None and enc.timer.enabled
         if NATIVE_BACKWARD and enc.debug is None and not timed:
