@@ -1370,7 +1370,8 @@ extern "C" int rpc_spconv_rulebook_build(const int* coors, int N, const int* out
   hipStream_t st = (hipStream_t)stream;
   Shape so{out_shape[0], out_shape[1], out_shape[2], out_shape[3]};
   KGeom g = geom(ksize, stride, pad);
-  if (g.K > MAXK || (long long)N * g.K >= (1LL << 31) - BLK) return RPC_ERR_ARG;
+  if (g.K > MAXK) return RPC_ERR_UNSUPPORTED;   // as rpc_spconv_rulebook_count answers the same ksize
+  if ((long long)N * g.K >= (1LL << 31) - BLK) return RPC_ERR_ARG;
   size_t n = (size_t)N * g.K + 1;
   const unsigned* hmask = (const unsigned*)ws + (N + 1);
   int* pos = (int*)((char*)ws + al(n * sizeof(int)));

@@ -8,7 +8,9 @@ from oracle import voxelize as ov
 from oracle.sparse_encoder import OracleSparseEncoder, implementation_masks, spconv_pairs, subm_pairs
 from robustpointclouds_amd.sparse_encoder import SparseEncoder
 from robustpointclouds_amd.synthetic import KITTI_PC_RANGE, KITTI_VOXEL_SIZE, kitti_frame
+from tests import _sparse_cases as sc
 from tests._dense_masks import FlipStats
+from tests._sparse_hip import hip_strided, hip_subm
 
 pytestmark = pytest.mark.gpu
 FLIP_PRE_MAX = 1e-4   # an adopted ReLU decision float64 takes differently lies within this of 0 (x channel max |act|)
@@ -98,6 +100,24 @@ def test_rulebooks_match_oracle_pairs():
     assert sum(len(a) for a, _ in sub) > 0
     oc, sp = spconv_pairs(c, (2, 21, 800, 704), (3, 3, 3), (2, 2, 2), (1, 1, 1))
     assert oc.shape[0] > 0
+    # the HIP rulebooks of the same two convolutions on these frames, matched with the oracle's pairs by coordinate
+    # as sets of (k, in coordinate, out coordinate): row numbering is free, every neighbour is not
+    def oracle_set(pairs, c_out):
+        return {(k, tuple(a), tuple(b)) for k, (ri, ro) in enumerate(pairs)
+                for a, b in zip(c[ri].tolist(), c_out[ro].tolist())}
+    shape, geom = (2, 41, 1600, 1408), ((3, 3, 3), (2, 2, 2), (1, 1, 1))
+    assert tuple(enc.shapes[0]) == shape[1:] and tuple(enc.shapes[1]) == (21, 800, 704)
+    assert sc.out_shape(shape, *geom) == (2, 21, 800, 704)
+    nbr = hip_subm(coors, shape, enc.grid(0, 2, dev)).cpu().numpy()
+    assert sc.pair_set(nbr, c, c) == oracle_set(sub, c)
+    n_out, hip_oc, nbr_out, nbr_in = hip_strided(coors, shape, geom, enc.grid(1, 2, dev))
+    hip_oc = hip_oc.cpu().numpy().astype(np.int64)
+    assert n_out == oc.shape[0]
+    assert sc.pair_set(nbr_out.cpu().numpy(), c, hip_oc) == oracle_set(sp, oc)
+    i, k = np.nonzero(nbr_in.cpu().numpy() >= 0)
+    assert len(i) == sum(len(a) for a, _ in sp)
+    for g in enc._grids.values():
+        assert int((g != -1).sum().item()) == 0
 
 
 def test_bf16_perf_mode_close_to_oracle():
