@@ -799,6 +799,44 @@ typedef struct {
 int rpc_center_decode(const RpcCenterDecodeCfg* cfg, const float* hm, const float* box, const int* topk,
                       float* boxes, float* scores, int* labels, int* valid, void* stream);
 
+/* ------------------------------------------------------------------ KITTI BEV / 3D average precision
+ * The device part of the KITTI evaluator (robustpointclouds_amd/kitti_eval.py; DESIGN.md "KITTI average
+ * precision"), restating mmdet3d v1.x evaluation/functional/kitti_utils/eval.py in the LiDAR frame. Frames are
+ * ragged: det [sum Nd][7] and gt [sum Ng][7] fp32 LiDAR boxes (x, y, z of the BOTTOM face, dx, dy, dz, yaw),
+ * det_off / gt_off [frames + 1] device int32 (first row of each frame; counts are clamped to [0, max_det] /
+ * [0, max_gt]), ov_off [frames + 1] device int64 (first element of each frame's [Nd][Ng] overlap matrix).
+ * max_det <= RPC_KITTI_MAX_DET and max_gt <= RPC_KITTI_MAX_GT, else RPC_ERR_UNSUPPORTED; null pointers and
+ * negative counts give RPC_ERR_ARG; either way nothing is launched. */
+#define RPC_KITTI_MAX_DET 512
+#define RPC_KITTI_MAX_GT 128
+#define RPC_KITTI_MAX_THR 41
+#define RPC_KITTI_NO_SCORE (-10000000.0f)
+
+/* ov[ov_off[f] + j * Ng + i] = overlap of detection j and ground truth i of frame f: mode 0 rotated BEV IoU of
+ * the footprints, mode 1 3D IoU (footprint intersection x z-interval overlap / union volume). Finite in [0, 1]
+ * for every finite input, exactly 0 when any of the six extents is <= 0, exactly 1 for identical boxes. Frames
+ * with no detection or no ground truth write nothing. */
+int rpc_kitti_overlaps(const float* det, const int* det_off, const float* gt, const int* gt_off,
+                       const long long* ov_off, int frames, int max_det, int max_gt, int mode, float* ov,
+                       void* stream);
+
+/* The greedy matcher of compute_statistics_jit. A group is one (class, difficulty, overlap table): group g reads
+ * the flags of row g / ntab — flag_det [groups / ntab][n_det] and flag_gt [groups / ntab][n_gt] int8 in
+ * {-1, 0, 1}, n_det = sum Nd, n_gt = sum Ng — and its minimum overlap min_ov[g] (device fp32). score [n_det].
+ * Pass 1 (no threshold): tp_score [groups][n_gt] gets, at each ground truth's row, the score of the detection
+ * matched to it when both are valid (flag 0), else RPC_KITTI_NO_SCORE. */
+int rpc_kitti_match_scores(const float* ov, const long long* ov_off, const int* det_off, const int* gt_off,
+                           int frames, int max_det, int max_gt, const float* score, const signed char* flag_det,
+                           const signed char* flag_gt, long long n_det, long long n_gt, const float* min_ov,
+                           int groups, int ntab, float* tp_score, void* stream);
+/* Pass 2: for group g and each of its nthr[g] <= RPC_KITTI_MAX_THR thresholds thr[g][k] (device, row pitch
+ * RPC_KITTI_MAX_THR), counts[g][k] = (tp, fp, fn) summed over all frames (device int32
+ * [groups][RPC_KITTI_MAX_THR][3]; zeroed here, then integer atomics: the result does not depend on order). */
+int rpc_kitti_match_counts(const float* ov, const long long* ov_off, const int* det_off, const int* gt_off,
+                           int frames, int max_det, int max_gt, const float* score, const signed char* flag_det,
+                           const signed char* flag_gt, long long n_det, long long n_gt, const float* min_ov,
+                           int groups, int ntab, const float* thr, const int* nthr, int* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

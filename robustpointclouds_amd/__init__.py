@@ -1,0 +1,1 @@
+from .evaluate import evaluate, robustness_report  # noqa: F401

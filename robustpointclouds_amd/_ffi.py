@@ -131,6 +131,10 @@ class RpcCenterDecodeCfg(C.Structure):
 
 
 NMS_MAX_N = 4096   # include/rpc_hip.h RPC_NMS_MAX_N
+KITTI_MAX_DET = 512   # include/rpc_hip.h RPC_KITTI_MAX_DET
+KITTI_MAX_GT = 128    # RPC_KITTI_MAX_GT
+KITTI_MAX_THR = 41    # RPC_KITTI_MAX_THR
+KITTI_NO_SCORE = -10000000.0   # RPC_KITTI_NO_SCORE
 
 # name -> (restype, argtypes); every symbol here must be exported by the .so
 SIGNATURES = {
@@ -259,6 +263,11 @@ SIGNATURES = {
     "rpc_anchor_decode": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, C.POINTER(C.c_longlong), vp,
                                 vp, vp, vp]),
     "rpc_center_decode": (i32, [C.POINTER(RpcCenterDecodeCfg), vp, vp, vp, vp, vp, vp, vp, vp]),
+    "rpc_kitti_overlaps": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
+    "rpc_kitti_match_scores": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, C.c_longlong, C.c_longlong, vp, i32,
+                                     i32, vp, vp]),
+    "rpc_kitti_match_counts": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, C.c_longlong, C.c_longlong, vp, i32,
+                                     i32, vp, vp, vp, vp]),
 }
 
 
