@@ -1,4 +1,5 @@
-"""Shared inputs and float64 references for the sparse rulebook and fp32 sparse-conv kernel tests (no GPU code).
+"""Shared inputs and float64 references for the sparse rulebook and the fp32 and 16-bit sparse-conv kernel tests (no
+GPU code).
 
 Voxel sets on tiny grids that hold the places where a rulebook goes wrong (faces and corners of the volume, the
 seam between two frames of the linear grid, a voxel with no neighbour), rulebooks by brute force over a Python
@@ -285,3 +286,95 @@ def bnb_vec(c, gen):
     return torch.cat([torch.rand(c, generator=gen) + 0.5, torch.randn(c, generator=gen) * 0.3,
                       torch.randn(c, generator=gen) * 0.3, torch.randn(c, generator=gen) * 0.2,
                       torch.rand(c, generator=gen) + 0.5])
+
+
+# ------------------------------------------------------------------ 16-bit operands: the perf mode's GEMM family
+# Rows and weights drawn on the 16-bit grid are read back unchanged by the float64 references below, every product of
+# two of them is exact in fp32, and the weight-tile prep rounds nothing: what is left is the fp32 accumulation.
+H16 = (torch.bfloat16, torch.float16)      # indexed by RPC_H16_BF16, RPC_H16_F16
+
+
+def r8(c):
+    return (c + 7) // 8 * 8
+
+
+def r16(c):
+    return (c + 15) // 16 * 16
+
+
+def r32(c):
+    return (c + 31) // 32 * 32
+
+
+def h16_rows(n, c, gen, fmt, scale=1.0):
+    """operand rows [n, round8(c)] in H16[fmt]: randn * scale rounded to the format, padding columns zero (the
+    producers' contract: the GEMM reads those columns)"""
+    h = torch.zeros((n, r8(c)), dtype=H16[fmt])
+    h[:, :c] = (torch.randn((n, c), generator=gen) * scale).to(H16[fmt])
+    return h
+
+
+def h16_weights(K, ci, co, gen, fmt, scale=0.1):
+    """fp32 W [K, ci, co] whose every value lies on the grid of H16[fmt]"""
+    return (torch.randn((K, ci, co), generator=gen) * scale).to(H16[fmt]).float()
+
+
+def sat_f16(x):
+    """fp32 values as the fp16 producers see them: finite ones beyond +-65504 become +-65504, inf / NaN stay"""
+    x = torch.as_tensor(x).float()
+    big = torch.isfinite(x) & (x.abs() > 65504.0)
+    return torch.where(big, torch.copysign(torch.full_like(x, 65504.0), x), x)
+
+
+def to_h16(x, fmt):
+    """fp32 -> H16[fmt] as the kernels round: to nearest even, fp16 saturated first"""
+    x = torch.as_tensor(x).float()
+    return (sat_f16(x) if fmt else x).to(H16[fmt])
+
+
+def weight_tiles_ref(W, dgrad, fmt):
+    """The layout include/rpc_hip.h states for rpc_spconv_prep_weight_bf16: W [K, ci, co] -> forward tiles
+    [K, round16(co), round32(ci)] (tile[k, n, c] = W[k, c, n]), data-gradient tiles [K, round16(ci), round32(co)]
+    (tile[k, n, c] = W[k, n, c]), zero padded, in H16[fmt]"""
+    W = torch.as_tensor(W).float()
+    B = W if dgrad else W.transpose(1, 2)
+    t = torch.zeros((W.shape[0], r16(B.shape[1]), r32(B.shape[2])), dtype=H16[fmt])
+    t[:, :B.shape[1], :B.shape[2]] = to_h16(B, fmt)
+    return t
+
+
+def gather_gemm_ref(a, mp, rev, B):
+    """out[r] = sum_k a[mp[r, k'], :kg] . B[k], k' = K-1-k if rev else k, for ready rows a (any dtype, at least kg
+    columns) and B [K, kg, ng]; returns (out, S), S = sum |a| |B| per element. One contraction over the gathered
+    rows [n, K, kg] (a missing neighbour gathers zeros), not conv_ref's loop over offsets."""
+    B = _d(B)
+    K, kg, _ = B.shape
+    a = _d(a)[:, :kg]
+    mp = torch.as_tensor(mp).long()
+    assert mp.shape[1] == K
+    if rev:
+        mp = mp.flip(1)
+    G = a[mp.clamp_min(0)] * (mp >= 0).unsqueeze(-1)
+    return torch.einsum("rkc,kcn->rn", G, B), torch.einsum("rkc,kcn->rn", G.abs(), B.abs())
+
+
+def gather_wgrad_ref(h, nbr, dz):
+    """dW[k] = sum_r h[nbr[r, k], :ci]^T dz[r, :co] for ready rows; h and dz carry exactly ci and co columns.
+    Returns (dW, S, n_k): S = sum |h| |dz| per element, n_k [K] the number of rows that use offset k."""
+    h, dz = _d(h), _d(dz)
+    nbr = torch.as_tensor(nbr).long()
+    ok = (nbr >= 0).double()
+    G = h[nbr.clamp_min(0)] * ok.unsqueeze(-1)
+    return (torch.einsum("rkc,rn->kcn", G, dz), torch.einsum("rkc,rn->kcn", G.abs(), dz.abs()),
+            ok.sum(0).long())
+
+
+def infer_ref(acc, fold, res=None):
+    """The eval-mode epilogue y = relu(acc * scale + shift (+ res)) with fold = scale, shift [2C]; returns (y, M),
+    M = |acc * scale| + |shift| + |res|, the magnitude its roundings are relative to"""
+    acc = _d(acc)
+    sc, sh = _d(fold).view(2, -1)
+    pre, M = acc * sc + sh, (acc * sc).abs() + sh.abs()
+    if res is not None:
+        pre, M = pre + _d(res), M + _d(res).abs()
+    return torch.relu(pre), M
