@@ -837,6 +837,40 @@ int rpc_kitti_match_counts(const float* ov, const long long* ov_off, const int* 
                            const signed char* flag_gt, long long n_det, long long n_gt, const float* min_ov,
                            int groups, int ntab, const float* thr, const int* nthr, int* counts, void* stream);
 
+/* ------------------------------------------------------------------ nuScenes detection score
+ * The device part of the nuScenes evaluator (robustpointclouds_amd/nuscenes_eval.py; DESIGN.md "nuScenes
+ * detection score"), restating nuscenes-devkit eval/detection (detection_cvpr_2019) in the LiDAR frame. Frames
+ * are ragged: det_off / gt_off [frames + 1] device int32 (first row of each frame; inside the kernel rows and
+ * counts are clamped to [0, n_det] / [0, n_gt] and to max_det / max_gt, so bad offsets cannot index out of
+ * bounds). max_det <= RPC_NUS_MAX_DET, max_gt <= RPC_NUS_MAX_GT and n_thr <= RPC_NUS_MAX_THR, else
+ * RPC_ERR_UNSUPPORTED; null pointers and negative counts give RPC_ERR_ARG; either way nothing is launched. Zero
+ * frames, zero detections or zero thresholds is a successful no-op. */
+#define RPC_NUS_MAX_DET 512
+#define RPC_NUS_MAX_GT 512
+#define RPC_NUS_MAX_THR 8
+
+/* The greedy centre-distance matcher for every (frame, class, threshold). det_xy [n_det][2] / gt_xy [n_gt][2]
+ * fp32 centres, det_label / gt_label int32, det_keep / gt_keep int8 (0: filtered, never counts); the detections
+ * stand in evaluation order inside each frame. For class c in [0, n_classes) and threshold thr[t] (device fp32
+ * [n_thr]) the kept detections of c are walked in order; each takes, of the kept ground truths of c in its frame
+ * not taken yet for (c, t), the one at the smallest squared distance fl(fl(dx dx) + fl(dy dy)) (fp32, every
+ * operation rounded; the lowest row of equal distances) if that is < fl(thr thr). match [n_thr][n_det] int32: the
+ * GLOBAL row of the ground truth taken, or -1. The result does not depend on the launch geometry. */
+int rpc_nus_match(const float* det_xy, const int* det_label, const signed char* det_keep, const int* det_off,
+                  const float* gt_xy, const int* gt_label, const signed char* gt_keep, const int* gt_off, int frames,
+                  int max_det, int max_gt, long long n_det, long long n_gt, int n_classes, const float* thr,
+                  int n_thr, int* match, void* stream);
+
+/* The true-positive errors of detection j against ground truth match[j] (one row of rpc_nus_match's output;
+ * < 0 or >= n_gt: not matched, all five NaN). det [n_det][9] / gt [n_gt][9] fp32 (x, y, z, dx, dy, dz, yaw, vx,
+ * vy). err [n_det][5] fp32 = (trans, scale, orient, vel, attr): xy centre distance; 1 - IoU of the boxes aligned
+ * in centre and yaw (1 when any extent is <= 0); |((yaw_gt - yaw_det + p/2) floor-mod p) - p/2| with p =
+ * period[j] (device fp32 [n_det]: pi for a barrier, else 2 pi); the norm of the velocity difference (NaN for a
+ * NaN ground-truth velocity); 0 / 1 for equal / different det_attr[j] and gt_attr[match[j]] (device int32), NaN
+ * when the ground truth's is < 0. */
+int rpc_nus_tp_errors(const float* det, const float* gt, const int* match, const float* period, const int* det_attr,
+                      const int* gt_attr, long long n_det, long long n_gt, float* err, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -135,6 +135,9 @@ KITTI_MAX_DET = 512   # include/rpc_hip.h RPC_KITTI_MAX_DET
 KITTI_MAX_GT = 128    # RPC_KITTI_MAX_GT
 KITTI_MAX_THR = 41    # RPC_KITTI_MAX_THR
 KITTI_NO_SCORE = -10000000.0   # RPC_KITTI_NO_SCORE
+NUS_MAX_DET = 512   # RPC_NUS_MAX_DET
+NUS_MAX_GT = 512    # RPC_NUS_MAX_GT
+NUS_MAX_THR = 8     # RPC_NUS_MAX_THR
 
 # name -> (restype, argtypes); every symbol here must be exported by the .so
 SIGNATURES = {
@@ -268,6 +271,9 @@ SIGNATURES = {
                                      i32, vp, vp]),
     "rpc_kitti_match_counts": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, C.c_longlong, C.c_longlong, vp, i32,
                                      i32, vp, vp, vp, vp]),
+    "rpc_nus_match": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.c_longlong, C.c_longlong, i32, vp, i32,
+                            vp, vp]),
+    "rpc_nus_tp_errors": (i32, [vp, vp, vp, vp, vp, vp, C.c_longlong, C.c_longlong, vp, vp]),
 }
 
 

@@ -35,11 +35,15 @@ def evaluate(model, batches, metric, attacked: bool = False) -> dict:
     return metric.compute()
 
 
-def robustness_report(model, batches, class_names, min_overlaps=None) -> dict:
+def robustness_report(model, batches, class_names, min_overlaps=None, metric=None) -> dict:
     """{"clean": AP without the attack, "attacked": AP inside attack_eval(), "drop": clean - attacked per key}
-    over the same batches (a list, or any iterable that can be walked twice)."""
+    over the same batches (a list, or any iterable that can be walked twice). metric: an object with reset /
+    update / compute (nuscenes_eval.NuScenesDetectionScore for AdversarialCenterPoint) to use in place of the
+    KittiAP built from `class_names` and `min_overlaps`, which are then ignored. For a metric's error keys
+    (mATE, ..._err) a negative drop means the error GREW under attack; a NaN value gives a NaN drop."""
     batches = batches if isinstance(batches, (list, tuple)) else list(batches)
-    metric = KittiAP(class_names, min_overlaps)
+    if metric is None:
+        metric = KittiAP(class_names, min_overlaps)
     clean = evaluate(model, batches, metric, attacked=False)
     attacked = evaluate(model, batches, metric, attacked=True)
     return {"clean": clean, "attacked": attacked, "drop": {k: clean[k] - attacked[k] for k in clean}}

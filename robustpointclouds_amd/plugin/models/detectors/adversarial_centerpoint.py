@@ -16,9 +16,13 @@ perturbation_l2_norm.
 Documented fix (SURVEY.md finding 5): the reference stores the perturber's second output — its loss
 DICT — as `_current_l2_norm` (:81) and then multiplies / isnan()s it (:247, :252), which raises once
 `_epoch >= 3`; here `_current_l2_norm` is that dict's 'l2_norm' scalar, the value the code means.
+
+`attack_eval()` is the attacked evaluation: inside the block the gate also opens in eval mode and the perturber
+runs its eval forward (the recipe of evaluate_kitti_adversarial_attack.py, as AdversarialVoxelNet.attack_eval).
 """
 from __future__ import annotations
 
+from contextlib import contextmanager
 from typing import Dict, List
 
 import torch
@@ -56,6 +60,29 @@ class AdversarialCenterPoint(CenterPoint):
         self.regularization_weight = regularization_weight
         self._current_l2_norm = None
         self._epoch = 0
+        self._attack_eval = False
+
+    def _gate(self):
+        if getattr(self, "_attack_eval", False):
+            return self.adversary is not None and self._epoch >= 3   # attacked evaluation: whatever `training` is
+        return self.training and self._epoch >= 3                                      # :65
+
+    @contextmanager
+    def attack_eval(self):
+        """Attacked evaluation, the contract of AdversarialVoxelNet.attack_eval(): inside the block the perturber
+        runs although the detector is in eval mode (adversary present and `_epoch >= 3`). The reference has no
+        attacked nuScenes evaluation of its own — its evaluate_nuscenes_adversarial.py runs the stock test loop
+        in eval mode, where the gate `self.training and self._epoch >= 3` (:65) never opens — so this is the
+        KITTI recipe (evaluate_kitti_adversarial_attack.py:23-62) applied to CenterPoint. Every submodule stays
+        in eval mode, so the perturber takes its eval forward (running-statistics BatchNorm, eval bounds), which
+        `self.adversary.training == False` already selects. No module's `training` changes; the previous
+        `_attack_eval` is restored when the block exits, also when it raises."""
+        prev = getattr(self, "_attack_eval", False)
+        self._attack_eval = True
+        try:
+            yield self
+        finally:
+            self._attack_eval = prev
 
     def extract_pts_feat(self, voxel_dict, points=None, img_feats=None, batch_input_metas=None):
         if self.adversary is None:
@@ -65,7 +92,7 @@ class AdversarialCenterPoint(CenterPoint):
         if hasattr(self.pts_middle_encoder, "coors_ready"):
             self.pts_middle_encoder.coors_ready(coors)
         l2 = None
-        if self.training and self._epoch >= 3:
+        if self._gate():
             if isinstance(self.pts_voxel_encoder, HardSimpleVFE):
                 feats, loss_dict, _, _ = self.adversary.perturb_voxels(voxels, npts, self.pts_voxel_encoder.num_features)
             else:
