@@ -651,6 +651,60 @@ int rpc_augment_boxes(float* boxes, long long* labels, int batch, int max_gts, c
                       const float* pc_range /* host [6] */, void* stream);
 
 
+/* ------------------------------------------------------------------ §8(f2b) GT-database augmentation
+ * ObjectSample and ObjectNoise of configs/_base_/kitti-3d-car.py:42-68 and their primitive, points in
+ * rotated boxes (upstream mmdet3d ObjectSample / DataBaseSampler.sample_class_v2 / noise_per_object_v3_ and
+ * mmcv points_in_boxes; not vendored, the rules are stated in DESIGN.md "GT-database augmentation").
+ * Box = (x, y, z, dx, dy, dz, yaw), z the bottom face; a box exists iff its label (int64) is >= 0 and its
+ * extents are positive. Points: [P][F] fp32, B frames back to back with device frame_offsets [B+1]; rows
+ * past frame_offsets[B] belong to no frame. Every random number is drawn on the host; no entry needs a
+ * host read. Null pointers / negative counts: RPC_ERR_ARG; above a cap: RPC_ERR_UNSUPPORTED; either way
+ * nothing is launched and no output is written. Zero points, frames, boxes or candidates: a valid no-op
+ * that still writes its outputs.
+ *
+ * rpc_points_in_boxes: boxes [B][M][7], labels [B][M], M <= RPC_GT_MAX_BOXES. first [P]: lowest-index
+ * existing box of the point's frame that contains it (strict in the box's plane, closed in z), or -1;
+ * mask (may be NULL) [P][ceil(M/32)]: bit m = box m contains the point; counts [B][M]: points inside each
+ * box. A point with a NaN coordinate is inside nothing.
+ *
+ * rpc_object_sample_select: one frame's candidates cand [B][S] (database indices, -1 = none) in class-draw
+ * order with their draw ids draw [B][S]; S <= RPC_GT_MAX_CAND. Candidate i is accepted iff its footprint
+ * collides with no existing box of the frame, no candidate accepted before it and no later candidate of its
+ * own draw; an accepted box / label goes to the next free (label < 0) slot of gt_boxes [B][M][7] /
+ * gt_labels [B][M] (in place); without a free slot it is rejected. accept [B][S]: the slot, or -1.
+ *
+ * rpc_object_sample_points: out_points [cap][F] = per frame the accepted objects' points (db_points
+ * [Q][F] centred on their box, db_offsets [N+1]) translated by the box (x, y, z), in acceptance order, then
+ * the frame's points inside no accepted box, in order; frames back to back, out_offsets [B+1], NaN rows
+ * after the last frame. cap >= frame_offsets[B] + the point counts of all candidates.
+ *
+ * rpc_object_noise_select: loc [B][M][T][3], rot [B][M][T], T <= RPC_GT_MAX_TRY. Boxes in index order:
+ * chosen[i] = the first try j whose footprint (centre + loc[i][j][:2], yaw + rot[i][j]) collides with no
+ * current footprint of another existing box (moved for earlier boxes that found a try), or -1.
+ * rpc_object_noise_apply: every point moves with the first existing box, in its original pose, that
+ * contains it: p' = R(rot) (p - c_xy) + c_xy + loc (R counter-clockwise), z' = z + loc_z; identity when
+ * chosen is -1. Then the boxes: centre += loc, yaw += rot, in place. */
+#define RPC_GT_MAX_BOXES 128   /* = RPC_KITTI_MAX_GT */
+#define RPC_GT_MAX_CAND 128
+#define RPC_GT_MAX_TRY 512
+int rpc_points_in_boxes(const float* points, int num_features, int total_points, const int* frame_offsets,
+                        int batch, const float* boxes, const long long* labels, int max_gts, int* first,
+                        unsigned* mask, int* counts, void* stream);
+int rpc_object_sample_select(const float* db_boxes, const long long* db_labels, int num_objects, const int* cand,
+                             const int* draw, int batch, int max_cand, float* gt_boxes, long long* gt_labels,
+                             int max_gts, int* accept, void* stream);
+size_t rpc_object_sample_points_workspace_size(int total_points, int batch, int max_cand);
+int rpc_object_sample_points(const float* points, int num_features, int total_points, const int* frame_offsets,
+                             int batch, const float* db_points, const int* db_offsets, const float* db_boxes,
+                             int num_objects, const int* cand, const int* accept, int max_cand, float* out_points,
+                             int out_capacity, int* out_offsets, void* workspace, size_t ws_bytes, void* stream);
+int rpc_object_noise_select(const float* gt_boxes, const long long* gt_labels, int batch, int max_gts,
+                            const float* loc, const float* rot, int num_try, int* chosen, void* stream);
+int rpc_object_noise_apply(float* points, int num_features, int total_points, const int* frame_offsets, int batch,
+                           float* gt_boxes, const long long* gt_labels, int max_gts, const float* loc,
+                           const float* rot, int num_try, const int* chosen, void* stream);
+
+
 /* ------------------------------------------------------------------ §8(f3) CenterHead targets + losses
  * Replaces upstream mmdet3d `CenterHead.get_targets` / `loss_by_feat` (dense_heads/centerpoint_head.py;
  * draw_heatmap_gaussian, gaussian_radius, mmdet GaussianFocalLoss + L1Loss) as configured by

@@ -135,6 +135,9 @@ KITTI_MAX_DET = 512   # include/rpc_hip.h RPC_KITTI_MAX_DET
 KITTI_MAX_GT = 128    # RPC_KITTI_MAX_GT
 KITTI_MAX_THR = 41    # RPC_KITTI_MAX_THR
 KITTI_NO_SCORE = -10000000.0   # RPC_KITTI_NO_SCORE
+GT_MAX_BOXES = 128    # RPC_GT_MAX_BOXES
+GT_MAX_CAND = 128     # RPC_GT_MAX_CAND
+GT_MAX_TRY = 512      # RPC_GT_MAX_TRY
 NUS_MAX_DET = 512   # RPC_NUS_MAX_DET
 NUS_MAX_GT = 512    # RPC_NUS_MAX_GT
 NUS_MAX_THR = 8     # RPC_NUS_MAX_THR
@@ -230,6 +233,13 @@ SIGNATURES = {
     "rpc_augment_points_workspace_size": (sz, [i32, i32]),
     "rpc_augment_points": (i32, [vp, i32, i32, vp, i32, vp, fp, i32, C.c_ulonglong, vp, vp, vp, sz, vp]),
     "rpc_augment_boxes": (i32, [vp, vp, i32, i32, vp, fp, vp]),
+    "rpc_points_in_boxes": (i32, [vp, i32, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp]),
+    "rpc_object_sample_select": (i32, [vp, vp, i32, vp, vp, i32, i32, vp, vp, i32, vp, vp]),
+    "rpc_object_sample_points_workspace_size": (sz, [i32, i32, i32]),
+    "rpc_object_sample_points": (i32, [vp, i32, i32, vp, i32, vp, vp, vp, i32, vp, vp, i32, vp, i32, vp, vp, sz,
+                                       vp]),
+    "rpc_object_noise_select": (i32, [vp, vp, i32, i32, vp, vp, i32, vp, vp]),
+    "rpc_object_noise_apply": (i32, [vp, i32, i32, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp]),
     "rpc_head_pack": (i32, [vp, i32, i32, vp, vp, i32, i32, C.c_longlong, vp]),
     "rpc_head_unpack_workspace_size": (sz, []),
     "rpc_head_unpack_grad": (i32, [vp, i32, i32, i32, vp, i32, C.c_longlong, vp, vp, sz, vp]),

@@ -16,8 +16,10 @@ rot_range ±pi/4, scale 0.95-1.05) -> PointsRangeFilter -> ObjectRangeFilter -> 
   boxes become label -1 padding).
   PointShuffle: upstream permutes with torch.randperm on the host RNG; here `shuffle="device"` is a
   seeded uniform permutation per frame computed on the GPU (same distribution, different stream).
-* ObjectSample (GT-database paste) and ObjectNoise need the KITTI info / db pickles and per-object
-  collision tests; they are not part of the GPU pipeline (no dataset in this build's scope).
+* ObjectSample (GT-database paste) and ObjectNoise, the two transforms in front of these, are
+  `gt_augment.GpuObjectSample` / `GpuObjectNoise` (csrc/gt_augment.hip); they hand this class points
+  with a NaN tail and device offsets, so the chain needs no host read either. Reading KITTI's db
+  pickles is not part of this build: `gt_augment.GtDatabase` is cropped from frames or built from objects.
 """
 from __future__ import annotations
 
