@@ -417,7 +417,8 @@ int rpc_sparse_backward(const RpcSparseLayer* layers, int nlayers, const void* g
 #define RPC_DMAP_P1 3 /* 1x1 (ConvTranspose2d k1 s1) */
 #define RPC_DMAP_U2 4 /* ConvTranspose2d k2 s2 (4 parities) */
 #define RPC_DMAP_G2 5 /* data gradient of U2 */
-/* out[orow][ooff + n] (+)= sum_{t,k} src[src_row(row,t)][k] * wt[t][n][k]; cin % 64 == 0, cout % 128 == 0;
+/* out[orow][ooff + n] (+)= sum_{t,k} src[src_row(row,t)][k] * wt[t][n][k]; cin % 64 == 0, cout % 128 == 0
+ * (RPC_DMAP_S1: cout % 64 == 0);
  * part (optional): [rpc_dense_conv_part_rows][2*cout] BatchNorm partial sums of the stored bf16 values */
 int rpc_dense_conv(int map, const void* src, int src_pitch, int cin, const void* wt, int cout, void* out,
                    int out_pitch, int out_offset, int accumulate, float* part, const int* row_img,
@@ -438,27 +439,35 @@ int rpc_dense_conv_bnbwd(const void* src, int src_pitch, int cin, const void* wt
                          void* stream);
 /* which kernel rpc_dense_conv launches for an RPC_DMAP_S1 call with `cout` outputs over row_img:
  * 0 = rpc::dn::k_conv3x3<0> (64-channel blocks), 1 = rpc::dn::k_conv3x3w<0> (128-channel LDS-DMA
- * blocks), 2 = rpc::dn::k_conv3x3x<0> (16x32-pixel x 128-channel LDS-DMA blocks), -1 = not an S1 call (per-kernel roofline attribution in bench.py) */
+ * blocks), 2 = rpc::dn::k_conv3x3x<0> (16x32-pixel x 128-channel LDS-DMA blocks), 3 = rpc::dn::k_conv3x3y<0, .>
+ * (16x16-pixel x 128-channel LDS-DMA blocks, two per CU), -1 = not an S1 call (per-kernel roofline attribution
+ * in bench.py). The 2 GB limit of kernels 2 and 3 is not consulted: for an image or weights of 2 GB and above
+ * rpc_dense_conv may run another kernel than the one named here, or return RPC_ERR_UNSUPPORTED */
 int rpc_dense_conv_s1_kernel(int map, int cout, const int* row_img);
-/* kernel-selection knob for A/B measurement (returns the previous value; value < 0 only reads it):
+/* kernel-selection knobs for A/B measurement and tests (returns the previous value; a value out of the knob's
+ * range, such as any value < 0, only reads it; an unknown knob returns RPC_ERR_ARG):
  * knob 0 = the S1 kernel for output channels that are a multiple of 128 (0: chosen by shape, default;
- * 1: the 64-channel register-staged kernel; 2: the 128-channel LDS-DMA kernel; 3: the 16x32-pixel
- * tile kernel; 4: the 16x16-pixel two-blocks-per-CU kernel); knob 1 = the S1 weight gradient for
- * 128-multiple channels (0: tap-sharing row-segment kernel with the next sub-step's operand reads issued
- * before this one's MFMAs, default; 1: per-tap kernel; 2: the row-segment kernel's former read-then-MFMA
- * loop); knob 4 = k_conv3x3x / k_conv3x3y loop variants and timing arms (128: x with operand reads a
- * quarter step ahead / y's former read-then-MFMA loop; bit-identical to the defaults); knob 5 = the
- * 64-channel-multiple k_conv3x3's output channels per block (0: 32 when the 64-channel grid is under one
- * round of two blocks per CU, default; 1: always 64; 2: always 32; bit-identical results); knob 8 = the
- * 16x16-pixel kernel's split tail (1: the items past the last whole round of one block per CU run as two
- * 64-channel blocks each when they fit one round, default; 0: off; bit-identical results); knob 9 = the row
- * mapping of rpc_dense_bn_apply / rpc_dense_bnbwd_apply (0: one contiguous chunk of rows per block, default;
- * 1: grid-stride batches; bit-identical results); knob 10 = the 16x16-pixel kernel's pre-activation prefetch for
- * rpc_dense_conv_bnbwd (1: the epilogue's first rows loaded during the last K-chunk, default; 0: all in the
- * epilogue; bit-identical results) */
+ *   1: the 64-channel register-staged kernel; 2: the 128-channel LDS-DMA kernel; 3: the 16x32-pixel
+ *   tile kernel; 4: the 16x16-pixel two-blocks-per-CU kernel);
+ * knob 1 = the S1 weight gradient (0 by shape: column-walk kernel where ci % 64 == 0 and co % 128 == 0, else
+ *   per-tap; 1 per-tap; 3 column walk);
+ * knob 2 = the grid order of the implicit-GEMM maps (0: flat, a tile's channel blocks adjacent, when there are two
+ *   channel blocks, default; 1: always 2-D; bit-identical results);
+ * knob 5 = the 64-channel-multiple k_conv3x3's output channels per block (0: 32 when the 64-channel grid is
+ *   under one round of two blocks per CU, default; 1: always 64; 2: always 32; bit-identical results);
+ * knob 6 = the column-walk weight gradient's strip width in pixels (0: the one of 32 / 64 / 96 that pads an image
+ *   row least, default; 32 / 64 / 96: that one);
+ * knob 8 = the 16x16-pixel kernel's split tail (1: the items past the last whole round of one block per CU run
+ *   as two 64-channel blocks each when they fit one round, default; 0: off; bit-identical results);
+ * knob 9 = the row mapping of rpc_dense_bn_apply / rpc_dense_bnbwd_apply (0: one contiguous chunk of rows per
+ *   block, default; 1: grid-stride batches; bit-identical results);
+ * knob 10 = the 16x16-pixel kernel's pre-activation prefetch for rpc_dense_conv_bnbwd (1: the epilogue's first
+ *   rows loaded during the last K-chunk, default; 0: all in the epilogue; bit-identical results).
+ * Knobs 4 and 7 (timing arms of the S1 kernels) and values 2 and 4 of knob 1 (the row-segment weight gradient)
+ * were removed with the code they selected. */
 int rpc_dense_tune(int knob, int value);
 /* dW (torch layout; kind 0 = Conv2d [co][ci][kh][kw], 1 = ConvTranspose2d [ci][co][kh][kw]) of the
- * forward map (S1/S2/P1/U2): sum over rows of x[src_row(row,t)][ci] * dz[row][co]; ci, co % 128 == 0 */
+ * forward map (S1/S2/P1/U2): sum over rows of x[src_row(row,t)][ci] * dz[row][co]; ci, co % 64 == 0 */
 size_t rpc_dense_wgrad_workspace_size(int map, const int* row_img, int ci, int co);
 int rpc_dense_wgrad(int map, int kind, const void* x, int x_pitch, int ci, const void* dz, int dz_pitch, int co,
                     const int* row_img, const int* src_img, const int* out_img, float* dW, void* workspace,

@@ -854,10 +854,7 @@ constexpr int XHI = 6;                         // halo DMA instructions per wave
 
 __device__ __forceinline__ int xswz(int x) { return (x >> 1) & 2; }
 
-// DBG (timing experiments only, rpc_dense_tune knob 4; outputs are garbage): bit 0 = no MFMAs, bit 1 =
-// no operand reads, bit 2 = no weight DMAs, bit 3 = no halo DMAs, bit 4 = no barriers in the K-loop,
-// bit 5 = the register-direct epilogue (8-byte stores from the accumulator layout)
-template <int DBG = 0>
+template <int DUMMY = 0>
 __global__ __launch_bounds__(WB, 2) void k_conv3x3x(C3 g) {
   // ONE LDS object: a second __shared__ array gives the accesses alias scopes, and the compiler then
   // waits for every LDS-DMA in flight (vmcnt(0)) before each step's operand reads
@@ -900,7 +897,6 @@ __global__ __launch_bounds__(WB, 2) void k_conv3x3x(C3 g) {
     wofs = (unsigned)(((n0 + r) * g.CIN + (j ^ xswz(r)) * 8) * 2);
   }
   auto issue_halo = [&](int kc, int hb) {
-    if (DBG & 8) return;
 #pragma unroll
     for (int m = 0; m < XHI; ++m)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(
@@ -909,7 +905,6 @@ __global__ __launch_bounds__(WB, 2) void k_conv3x3x(C3 g) {
   };
   const int wtap = g.COUT * g.CIN * 2;
   auto issue_w = [&](int s) {
-    if (DBG & 4) return;
     s = min(s, NS - 1);
     const int kc = s / 9, t = s - kc * 9;
     __builtin_amdgcn_raw_ptr_buffer_load_lds(
@@ -935,17 +930,15 @@ __global__ __launch_bounds__(WB, 2) void k_conv3x3x(C3 g) {
 #pragma unroll
   for (int s = 0; s < XWD; ++s) issue_w(s);
 
-  // DBG bit 128: operand fragments read a quarter step ahead (C3X_PSTEP, one barrier per step) instead of
-  // the partner groups staggered one phase (two barriers per step). Measured equal (100x88 256->256 63.8
-  // vs 62.4 us, 200x176 128->128 69.7 vs 69.7, profiles/r03_conv_pipe.log): the stagger already hides
-  // the reads here, unlike k_conv3x3y's, so the staggered loop stays the default
-  constexpr bool PIPE = (DBG & 128) != 0;
-  const int grp = PIPE ? 0 : w >> 2;
+  // The partner groups run staggered one phase (two barriers per step), as in k_conv3x3w. A loop that read the
+  // operand fragments a quarter step ahead instead (one barrier per step, as k_conv3x3y's) measured equal
+  // (100x88 256->256 63.8 vs 62.4 us, 200x176 128->128 69.7 vs 69.7, profiles/r03_conv_pipe.log): the stagger
+  // already hid the reads here, unlike k_conv3x3y's, so the staggered loop stayed and the other was removed.
+  // Timing arms that skipped the MFMAs, the operand reads, the DMAs or the barriers were removed with it.
+  const int grp = w >> 2;
   const bool live = ty0 + wp * 4 < g.H;
   static_assert(XWD == 4 && XHI == 6 && HTAP + XWD <= 8, "vmcnt immediates below");
-  // halo 0 + tile 0 (pipelined: + tile 1; tiles 2, 3 stay in flight)
-  if (PIPE) asm volatile("s_waitcnt vmcnt(2)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(3)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  asm volatile("s_waitcnt vmcnt(3)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // halo 0 + tile 0
   if (grp) asm volatile("s_barrier" ::: "memory");
   // per step: 1 weight DMA XWD tiles ahead (+ XHI halo DMAs at tap HTAP, after it); the tile of the next
   // step is retired by vmcnt(XWD - 1), or vmcnt(XWD - 1 + XHI) at taps HTAP .. HTAP + XWD - 1 while the
@@ -970,19 +963,15 @@ __global__ __launch_bounds__(WB, 2) void k_conv3x3x(C3 g) {
     const unsigned char* wt_ = wring + (s_ & (XWR - 1)) * XWTILE;                                             \
     constexpr int dy_ = (t) / 3, dx_ = (t) % 3;                                                               \
     bf16x8 av[4], bv[8];                                                                                      \
-    if (DBG & 2) {                                                                                            \
-      _Pragma("unroll") for (int i = 0; i < 4; ++i) av[i] = __builtin_bit_cast(bf16x8, make_uint4(lane, i, w, s_)); \
-      _Pragma("unroll") for (int j = 0; j < 8; ++j) bv[j] = __builtin_bit_cast(bf16x8, make_uint4(j, lane, s_, w)); \
-    }                                                                                                         \
-    if (LIVE && !(DBG & 2)) {                                                                                 \
+    if (LIVE) {                                                                                               \
       _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                           \
         av[i] = *(const bf16x8*)(wt_ + woff + i * 16 * XROW);                                                 \
       _Pragma("unroll") for (int j = 0; j < 8; ++j)                                                           \
         bv[j] = *(const bf16x8*)(hb_ + hoff[dx_] + ((j >> 1) + dy_) * XHP * XROW + (j & 1) * 16 * XROW);      \
     }                                                                                                         \
     if (grp) C3X_VMWAIT(t, LAST)                                                                              \
-    if (DBG & 16) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); else asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");                                           \
-    if (LIVE && !(DBG & 1)) {                                                                                 \
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");                                           \
+    if (LIVE) {                                                                                               \
       __builtin_amdgcn_s_setprio(1);                                                                          \
       _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                           \
         _Pragma("unroll") for (int j = 0; j < 8; ++j)                                                         \
@@ -990,82 +979,13 @@ __global__ __launch_bounds__(WB, 2) void k_conv3x3x(C3 g) {
       __builtin_amdgcn_s_setprio(0);                                                                          \
     }                                                                                                         \
     if (!grp) C3X_VMWAIT(t, LAST)                                                                             \
-    if (!(DBG & 16)) asm volatile("s_barrier" ::: "memory");                                                  \
+    asm volatile("s_barrier" ::: "memory");                                                                   \
   }
-  // pipelined form: a step's 32 MFMAs run as four quarters (the 4 weight fragments x the 2 halo fragments
-  // of one tile row); before quarter q's MFMAs the wave reads quarter q + 1's 2 halo fragments, before
-  // quarter 3's the next step's 4 weight fragments and its quarter-0 halo fragments, so every LDS read
-  // lies under the same wave's MFMAs (fragment registers: two 4-fragment weight buffers + a 2 x 2 halo
-  // ring = the former loop's 48). The next step's tile must then be published one step earlier: step s
-  // retires tile s + 2 (vmcnt(2), or vmcnt(8) while a halo chunk issued at step s - 2 .. s is younger),
-  // so a halo chunk issued at tap HTAP is retired at tap HTAP + 2 <= 7, before tap 8 reads its first
-  // fragments; its buffer was last read during step (kc - 1, 8). Tile s + 4 goes to ring slot
-  // (s + 4) & 7, last read during step s - 4. At the last step the reads for "step NS" hit valid LDS
-  // (clamped tile / halo) and are never used.
-#define C3X_PREAD_B(FB, tn, kn, qq)                                                                         \
-  {                                                                                                         \
-    const unsigned char* hb_ = hbuf + ((kn) & 1) * XHBUF;                                                   \
-    const int dy_ = (tn) / 3, dx_ = (tn) % 3;                                                               \
-    FB[0] = *(const bf16x8*)(hb_ + hoff[dx_] + ((qq) + dy_) * XHP * XROW);                                  \
-    FB[1] = *(const bf16x8*)(hb_ + hoff[dx_] + ((qq) + dy_) * XHP * XROW + 16 * XROW);                      \
-  }
-#define C3X_PREAD_A(FA, sn)                                                                                 \
-  {                                                                                                         \
-    const unsigned char* wt_ = wring + ((sn) & (XWR - 1)) * XWTILE;                                         \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i) FA[i] = *(const bf16x8*)(wt_ + woff + i * 16 * XROW);     \
-  }
-#define C3X_PMMA(FA, FB, qq)                                                                                \
-  __builtin_amdgcn_s_setprio(1);                                                                            \
-  _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                             \
-    _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                           \
-      acc[i][2 * (qq) + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(FA[i], FB[j], acc[i][2 * (qq) + j], 0, 0, 0); \
-  __builtin_amdgcn_s_setprio(0);
-#define C3X_PSTEP(t, FA, NA, LIVE)                                                                          \
-  {                                                                                                         \
-    const int s_ = kc * 9 + (t);                                                                            \
-    issue_w(s_ + XWD);                                                                                      \
-    if ((t) == HTAP) issue_halo(min(kc + 1, NKC - 1), (kc + 1) & 1);                                        \
-    if (LIVE) {                                                                                             \
-      C3X_PREAD_B(by, (t), kc, 1)                                                                           \
-      asm volatile("s_waitcnt lgkmcnt(2)" ::: "memory");                                                    \
-      C3X_PMMA(FA, bx, 0)                                                                                   \
-      C3X_PREAD_B(bx, (t), kc, 2)                                                                           \
-      asm volatile("s_waitcnt lgkmcnt(2)" ::: "memory");                                                    \
-      C3X_PMMA(FA, by, 1)                                                                                   \
-      C3X_PREAD_B(by, (t), kc, 3)                                                                           \
-      asm volatile("s_waitcnt lgkmcnt(2)" ::: "memory");                                                    \
-      C3X_PMMA(FA, bx, 2)                                                                                   \
-      C3X_PREAD_A(NA, s_ + 1)                                                                               \
-      C3X_PREAD_B(bx, ((t) + 1) % 9, kc + ((t) == 8), 0)                                                    \
-      asm volatile("s_waitcnt lgkmcnt(6)" ::: "memory");                                                    \
-      C3X_PMMA(FA, by, 3)                                                                                   \
-    }                                                                                                       \
-    if ((t) >= HTAP && (t) <= HTAP + 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");                    \
-    else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");                                                   \
-    asm volatile("s_barrier" ::: "memory");                                                                 \
-  }
-#define C3X_PKC(LIVE)                                                                                       \
-  C3X_PSTEP(0, a0, a1, LIVE) C3X_PSTEP(1, a1, a0, LIVE) C3X_PSTEP(2, a0, a1, LIVE)                          \
-  C3X_PSTEP(3, a1, a0, LIVE) C3X_PSTEP(4, a0, a1, LIVE) C3X_PSTEP(5, a1, a0, LIVE)                          \
-  C3X_PSTEP(6, a0, a1, LIVE) C3X_PSTEP(7, a1, a0, LIVE) C3X_PSTEP(8, a0, a1, LIVE)
-  if constexpr (PIPE) {
-    bf16x8 a0[4], a1[4], bx[2], by[2];
-    if (live) {
-      C3X_PREAD_A(a0, 0)
-      C3X_PREAD_B(bx, 0, 0, 0)
-      for (int kc = 0; kc < NKC; ++kc) {   // 9 steps (odd): the next chunk's weight fragments move back to a0
-        C3X_PKC(true)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) a0[i] = a1[i];
-      }
-    } else {
-      for (int kc = 0; kc < NKC; ++kc) { C3X_PKC(false) }
-    }
-  } else if (live) {
 #define C3X_KC(LIVE, LAST)                                                                                    \
   C3X_STEP(0, LIVE, LAST) C3X_STEP(1, LIVE, LAST) C3X_STEP(2, LIVE, LAST) C3X_STEP(3, LIVE, LAST)             \
   C3X_STEP(4, LIVE, LAST) C3X_STEP(5, LIVE, LAST) C3X_STEP(6, LIVE, LAST) C3X_STEP(7, LIVE, LAST)             \
   C3X_STEP(8, LIVE, LAST)
+  if (live) {
     for (int kc = 0; kc < NKC - 1; ++kc) { C3X_KC(true, false) }
     {
       const int kc = NKC - 1;
@@ -1081,16 +1001,11 @@ __global__ __launch_bounds__(WB, 2) void k_conv3x3x(C3 g) {
 #undef C3X_STEP
 #undef C3X_KC
 #undef C3X_VMWAIT
-#undef C3X_PKC
-#undef C3X_PSTEP
-#undef C3X_PMMA
-#undef C3X_PREAD_A
-#undef C3X_PREAD_B
-  if (!PIPE && !grp) asm volatile("s_barrier" ::: "memory");
+  if (!grp) asm volatile("s_barrier" ::: "memory");
   asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 
   // ---- epilogue: lane holds co = n0 + wc*64 + i*16 + 4q + r of pixel (wp*4 + (j >> 1), (j & 1)*16 + a15)
-  if (!g.accum && !(DBG & 32)) {
+  if (!g.accum) {
     // Staged through LDS (the pipeline buffers are drained): the bf16 tile [512 px][128 co] (256-byte
     // rows, 16-byte granule g of pixel p at slot g ^ (p & 15): the 16 pixels of one ds_write_b64 lane
     // group hit 16 slots), then written back as whole 256-byte pixel rows, 16 bytes per lane — a tile
@@ -1304,7 +1219,7 @@ __device__ __forceinline__ void c3y_vm_halo() {
 // ZPF (data gradients with fused BatchNorm-backward sums): the epilogue's first ZPN pre-activation rows are loaded during
 // the last K-chunk — issued after its last real weight tile (step 5); the later steps issue no weight DMAs (in every
 // launch: they were clamped repeats), so the loads stay in flight through steps 6-8 and the accumulator staging
-template <int DBG, int CH, bool ZPF = false>
+template <int CH, bool ZPF = false>
 __device__ __forceinline__ void conv3x3y_body(const C3& g, unsigned char* lds, const int tile, const int n0) {
   static_assert(CH == 128 || CH == 64, "k_conv3x3y: 128 or 64 output channels per block");
   constexpr int NI = CH / 16, WI = CH / 64;   // accumulator fragments per wave; weight DMAs per wave and step
@@ -1368,9 +1283,10 @@ __device__ __forceinline__ void conv3x3y_body(const C3& g, unsigned char* lds, c
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-  // operand fragments read a quarter step ahead (C3Y_PSTEP); DBG bit 128 (and the timing arms 1 / 16):
-  // the former loop, which reads a step's 12 fragments, waits for all of them, then runs its 32 MFMAs
-  // (200x176 128->128 72.6 -> 66.9 us, 128->256 113.9 -> 109.8 us, profiles/r03_conv_pipe.log)
+  // operand fragments are read a quarter step ahead (C3Y_PSTEP). The former loop, which read a step's 12
+  // fragments, waited for all of them and then ran its 32 MFMAs, was slower (200x176 128->128 72.6 -> 66.9 us,
+  // 128->256 113.9 -> 109.8 us, profiles/r03_conv_pipe.log) and was removed, with the timing arms that skipped
+  // the MFMAs, the K-loop or the stores.
   // ZPF: the epilogue's first ZPN pre-activation rows of this thread's 16-byte column chunk (see C3Y_PKCZ)
   constexpr int ZPN = 4, ZQ = ZPF ? ZPN : 0;   // ZQ: the prefetch loads outstanding after the last weight tile
   uint4 zpa[ZPF ? ZPN : 1];
@@ -1380,43 +1296,15 @@ __device__ __forceinline__ void conv3x3y_body(const C3& g, unsigned char* lds, c
     _Pragma("unroll") for (int k_ = 0; k_ < ZPN; ++k_) zpa[k_] =                                            \
         *(const uint4*)(g.bnz + ((size_t)(b * g.H + min(ty0 + k_, g.H - 1)) * g.W + zpx_) * g.COUT + zpch_); \
   }
-  constexpr bool PIPE = (DBG & (128 | 16 | 1)) == 0;
   issue_halo(0, 0);
 #pragma unroll
   for (int s = 0; s < WDIST; ++s) issue_w(s);
-  if constexpr (PIPE) issue_w(WDIST);
+  issue_w(WDIST);   // (its own statement: folded into the loop, the compiler clamps the tile index another way)
   const bool live = ty0 + w * 4 < g.H;
-  // halo 0 + tile 0 (+ tile 1 when pipelined: the youngest tile stays in flight)
+  // halo 0 + tiles 0, 1 (the youngest tile stays in flight)
   c3y_vm_tile<WI>();
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  // per step: issue the DMAs two steps ahead, read this step's 12 fragments, 32 MFMAs, retire the next
-  // step's tile (vmcnt(2); vmcnt(8) at taps HTAP, HTAP + 1 whose younger DMAs include the halo), barrier
-#define C3Y_STEP(t, LIVE)                                                                                     \
-  {                                                                                                           \
-    const int s_ = kc * 9 + (t);                                                                              \
-    issue_w(s_ + WDIST);                                                                                      \
-    if ((t) == HTAP) issue_halo(min(kc + 1, NKC - 1), (kc + 1) & 1);                                          \
-    if (LIVE && !(DBG & 1)) {                                                                                 \
-      const unsigned char* hb_ = hbuf + (kc & 1) * YHBUF;                                                     \
-      const unsigned char* wt_ = wring + (s_ & (WRING - 1)) * XWTILE;                                         \
-      constexpr int dy_ = (t) / 3, dx_ = (t) % 3;                                                             \
-      bf16x8 av[NI], bv[4];                                                                                    \
-      _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                           \
-        bv[j] = *(const bf16x8*)(hb_ + hoff[dx_] + (j + dy_) * YHP * XROW);                                   \
-      _Pragma("unroll") for (int i = 0; i < NI; ++i)                                                          \
-        av[i] = *(const bf16x8*)(wt_ + woff + i * 16 * XROW);                                                 \
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                      \
-      __builtin_amdgcn_s_setprio(1);                                                                          \
-      _Pragma("unroll") for (int i = 0; i < NI; ++i)                                                          \
-        _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                         \
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[i], bv[j], acc[i][j], 0, 0, 0);              \
-      __builtin_amdgcn_s_setprio(0);                                                                          \
-    }                                                                                                         \
-    if ((t) == HTAP || (t) == HTAP + 1) c3y_vm_halo<WI>();                                                        \
-    else c3y_vm_tile<WI>();                                                                                       \
-    asm volatile("s_barrier" ::: "memory");                                                                   \
-  }
-  // pipelined form: the 32 MFMAs of a step run as four quarters of 2 weight fragments x 4 halo
+  // the 32 MFMAs of a step run as four quarters of 2 weight fragments x 4 halo
   // fragments; before the MFMAs of quarter q the wave issues the reads of quarter q + 1 (2 weight
   // fragments), and before those of quarter 3 the reads of the next step's quarter 0 and its 4 halo
   // fragments (that tile was published by the previous step's barrier), so every LDS read lies under the
@@ -1492,7 +1380,7 @@ __device__ __forceinline__ void conv3x3y_body(const C3& g, unsigned char* lds, c
   C3Y_PSTEP(0, fb0, fb1, LIVE, 0) C3Y_PSTEP(1, fb1, fb0, LIVE, 0) C3Y_PSTEP(2, fb0, fb1, LIVE, 0)           \
   C3Y_PSTEP(3, fb1, fb0, LIVE, 0) C3Y_PSTEP(4, fb0, fb1, LIVE, 0) C3Y_PSTEP(5, fb1, fb0, LIVE, ZPF ? 1 : 0)  \
   C3Y_PSTEP(6, fb0, fb1, LIVE, 2) C3Y_PSTEP(7, fb1, fb0, LIVE, 2) C3Y_PSTEP(8, fb0, fb1, LIVE, 2)
-  if constexpr (PIPE) {
+  {
     bf16x8 ax[2], ay[2], fb0[4], fb1[4];
     if (live) {
       C3Y_PREAD_A(ax, 0, 0)
@@ -1513,33 +1401,7 @@ __device__ __forceinline__ void conv3x3y_body(const C3& g, unsigned char* lds, c
         C3Y_PKCZ(false)
       }
     }
-  } else if (DBG & 16) {
-  } else if (live) {
-    for (int kc = 0; kc < NKC; ++kc) {
-      C3Y_STEP(0, true)
-      C3Y_STEP(1, true)
-      C3Y_STEP(2, true)
-      C3Y_STEP(3, true)
-      C3Y_STEP(4, true)
-      C3Y_STEP(5, true)
-      C3Y_STEP(6, true)
-      C3Y_STEP(7, true)
-      C3Y_STEP(8, true)
-    }
-  } else {
-    for (int kc = 0; kc < NKC; ++kc) {
-      C3Y_STEP(0, false)
-      C3Y_STEP(1, false)
-      C3Y_STEP(2, false)
-      C3Y_STEP(3, false)
-      C3Y_STEP(4, false)
-      C3Y_STEP(5, false)
-      C3Y_STEP(6, false)
-      C3Y_STEP(7, false)
-      C3Y_STEP(8, false)
-    }
   }
-#undef C3Y_STEP
 #undef C3Y_PKC
 #undef C3Y_PKCZ
 #undef C3Y_ZISSUE
@@ -1547,10 +1409,8 @@ __device__ __forceinline__ void conv3x3y_body(const C3& g, unsigned char* lds, c
 #undef C3Y_PMMA
 #undef C3Y_PREAD_A
 #undef C3Y_PREAD_B
-  if constexpr (PIPE)   // every weight / halo DMA retired by the last steps' waits; ZPF: the pre-activation loads stay
-    asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"(ZQ) : "memory");
-  else
-    asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  // every weight / halo DMA was retired by the last steps' waits; ZPF: the pre-activation loads stay in flight
+  asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"(ZQ) : "memory");
 
   // ---- epilogue: lane holds co = n0 + i*16 + 4q + r of pixel (4w + j, a15)
   if (!g.accum) {
@@ -1564,7 +1424,7 @@ __device__ __forceinline__ void conv3x3y_body(const C3& g, unsigned char* lds, c
       const int zc_ = tid & 15, zx_ = min(tx0 + (tid >> 4), g.W - 1);
 #pragma unroll
       for (int k = 0; k < CT; ++k) {
-        if (ZPF && PIPE && k < ZPN) zpre[k] = zpa[k % (ZPF ? ZPN : 1)];
+        if (ZPF && k < ZPN) zpre[k] = zpa[k % (ZPF ? ZPN : 1)];
         else
           zpre[k] = *(const uint4*)(g.bnz + ((size_t)(b * g.H + min(ty0 + k, g.H - 1)) * g.W + zx_) * g.COUT + n0 +
                                     zc_ * 8);
@@ -1609,7 +1469,7 @@ __device__ __forceinline__ void conv3x3y_body(const C3& g, unsigned char* lds, c
         if (y >= g.H || x >= g.W) continue;
         const size_t pix = (size_t)(b * g.H + y) * g.W + x;
         const uint4 v = *(const uint4*)(tileb + p * 256 + ((c ^ (p & 15)) * 16));
-  if (!(DBG & 64)) *(uint4*)(g.out + pix * g.OP + g.OOFF + n0 + c * 8) = v;
+        *(uint4*)(g.out + pix * g.OP + g.OOFF + n0 + c * 8) = v;
         const unsigned u[4] = {v.x, v.y, v.z, v.w};
         const unsigned zu[4] = {zpre[k].x, zpre[k].y, zpre[k].z, zpre[k].w};
 #pragma unroll
@@ -1628,7 +1488,7 @@ __device__ __forceinline__ void conv3x3y_body(const C3& g, unsigned char* lds, c
       if (y >= g.H || x >= g.W) continue;
       const size_t pix = (size_t)(b * g.H + y) * g.W + x;
       const uint4 v = *(const uint4*)(tileb + p * 256 + ((c ^ (p & 15)) * 16));
-      if (!(DBG & 64)) *(uint4*)(g.out + pix * g.OP + g.OOFF + n0 + c * 8) = v;
+      *(uint4*)(g.out + pix * g.OP + g.OOFF + n0 + c * 8) = v;
       const unsigned u[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -1735,7 +1595,7 @@ __device__ __forceinline__ void conv3x3y_body(const C3& g, unsigned char* lds, c
 
 // the grid: the first nitems - ysplit items (tile-major, a tile's co-blocks adjacent, XCD-aware) one 128-channel
 // block each, then the last ysplit items as two 64-channel blocks each (dispatched last: the tail of the launch)
-template <int DBG = 0, bool ZPF = false>
+template <int DUMMY = 0, bool ZPF = false>
 __global__ __launch_bounds__(YB, 2) void k_conv3x3y(C3 g) {
   __shared__ __attribute__((aligned(1024))) unsigned char lds[YLDS];   // ONE LDS object (see k_conv3x3x)
   const int ncob = g.COUT >> 7;
@@ -1743,11 +1603,11 @@ __global__ __launch_bounds__(YB, 2) void k_conv3x3y(C3 g) {
   if ((int)blockIdx.x < nfull) {
     const int item = xcd_remap(blockIdx.x, nfull);
     const int tile = item / ncob;
-    conv3x3y_body<DBG, 128, ZPF>(g, lds, tile, (item - tile * ncob) * 128);
-  } else if constexpr (DBG == 0) {
+    conv3x3y_body<128, ZPF>(g, lds, tile, (item - tile * ncob) * 128);
+  } else {
     const int t = (int)blockIdx.x - nfull, item = nfull + (t >> 1);
     const int tile = item / ncob;
-    conv3x3y_body<0, 64, ZPF>(g, lds, tile, (item - tile * ncob) * 128 + (t & 1) * 64);
+    conv3x3y_body<64, ZPF>(g, lds, tile, (item - tile * ncob) * 128 + (t & 1) * 64);
   }
 }
 
@@ -1761,7 +1621,7 @@ struct WG {
   int XP;
   const u16* dz;  // output-side gradient rows [O pixels][DP] at channel offset 0
   int DP;
-  int CI, CO;     // multiples of 128
+  int CI, CO;     // multiples of 64 (k_wgrad_s1c: CO of 128)
   Img R, S, O;
   int M, rows_per;
   float* part;    // [chunks][T][CI][CO]
@@ -1891,296 +1751,15 @@ __global__ __launch_bounds__(BLK, 2) void k_wgrad(WG g) {
       }
 }
 
-// ------------------------------------------------------------------ 3x3 stride-1 weight gradient, taps sharing tiles
-// k_wgrad_s1: dW[t][ci][co] = sum_m x[src(m, t)][ci] dz[m][co] for the S1 map, with the output pixels
-// walked as SEG-pixel segments of one image row. A segment's dz tile (SEG rows) and its x tile of the
-// input row y + dy - 1 (SEG + 2 rows: columns x0 - 1 .. x0 + SEG, zero outside the image) feed all three
-// taps (dy, 0..2) of that row: tap dx reads x rows r + dx for output row r, so no per-tap masking is
-// needed (a segment never crosses an image row) and every staged byte serves 3 taps (k_wgrad stages
-// both operands once per tap). Block = (chunk of segments, dy, 128 x 128 (ci, co) tile), 8 waves as
-// 4 (ci, 32 each) x 2 (co, 64 each), each with 3 taps x 2 x 4 MFMA accumulator tiles (96 AGPRs; two
-// waves per SIMD, so one wave's LDS reads overlap the other's MFMAs).
-// Staging is LDS-DMA only, into a ring of WS_ST segment stages issued WS_ST - 1 segments ahead (no
-// VGPR round trip: the register-staged form of this kernel was bound by its one-segment-ahead
-// prefetch). Rows are unpadded 256-byte images whose 16-byte granules are XOR-swizzled by
-// ((row & 7) << 1) through the DMA's per-lane source address, which makes the transposed 8-byte
-// operand reads (ds_read_b64_tr_b16) of any 8 consecutive rows conflict-free. Every wave issues the
-// same number of DMA instructions per segment (surplus ones repeat the last: same bytes, same place),
-// so one counted vmcnt per segment retires exactly that segment's tiles before the barrier. Segments
-// whose source row y + dy - 1 lies outside the image are skipped (walked with counters, no
-// divisions); pixels past the row end are zero rows. Partial sums go to part[chunk][t][ci][co] like
-// k_wgrad (same k_wgrad_reduce).
-constexpr int WS_ST = 4;    // ring stages
-// ds_read_b64_tr_b16 at an LDS byte address, as inline asm (the caller waits on lgkmcnt)
-__device__ __forceinline__ s16x4 tr_read_asm(unsigned addr) {
-  s16x4 r;
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r) : "v"(addr));
-  return r;
-}
-constexpr int WSB = 512;    // threads
-template <int SEG, int PIPE = 0>
-__global__ __launch_bounds__(WSB, 1) void k_wgrad_s1(WG g, int nseg_x, int seg_per) {
-  constexpr int TC = 128, RB = 256;                              // 256-byte rows (128 bf16 channels)
-  constexpr int NWI = 2, NWJ = 4;                                // 16x16 tiles per wave (ci, co)
-  constexpr int XR = SEG + 2, NX = (XR + 3) / 4, ND = SEG / 4;   // DMA instructions (4 rows each)
-  constexpr int NI = NX + ND, PW = (NI + 7) / 8;                 // per segment, per wave
-  constexpr int XB = NX * 4 * RB, STB = XB + SEG * RB;           // x tile bytes, stage bytes
-  static_assert(SEG % 32 == 0 && WS_ST * STB <= 160 * 1024, "segment");
-  __shared__ __attribute__((aligned(1024))) unsigned char lds[WS_ST * STB];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int wci = w >> 1, wco = w & 1;
-  const int nco = g.CO / TC, ntile = (g.CI / TC) * nco;
-  const int lid = xcd_remap(blockIdx.x, gridDim.x);
-  const int chunk = lid / (3 * ntile), rest = lid - chunk * (3 * ntile);
-  const int dy = rest / ntile, tile = rest - dy * ntile;
-  const int ci0 = (tile / nco) * TC, co0 = (tile % nco) * TC;
-  const int H = g.R.H, W = g.R.W;
-  const int nseg = g.R.B * H * nseg_x;
-  const int sg0 = min(nseg, chunk * seg_per), sg1 = min(nseg, sg0 + seg_per);
-  const bool skip_top = dy == 0, skip_bot = dy == 2;   // source row outside the image at y = 0 / H - 1
-
-  // ---- segment walk (uniform): position of segment sg0, count of valid segments
-  int cx = sg0 % nseg_x, cby = sg0 / nseg_x;
-  int cy = cby % H, cb = cby / H;
-  int nvalid = 0;
-  {
-    int y = cy, left = sg1 - sg0, xs = cx;
-    while (left > 0) {
-      const int n = min(left, nseg_x - xs);
-      if (!((skip_top && y == 0) || (skip_bot && y == H - 1))) nvalid += n;
-      left -= n;
-      xs = 0;
-      if (++y == H) y = 0;
-    }
-  }
-  int ileft = sg1 - sg0;   // segments not yet passed by the issue cursor
-  auto skip_invalid = [&]() {
-    while (ileft > 0 && ((skip_top && cy == 0) || (skip_bot && cy == H - 1))) {
-      ileft -= nseg_x - cx;
-      cx = 0;
-      if (++cy == H) { cy = 0; ++cb; }
-    }
-  };
-  auto advance = [&]() {
-    --ileft;
-    if (++cx == nseg_x) {
-      cx = 0;
-      if (++cy == H) { cy = 0; ++cb; }
-    }
-  };
-
-  // ---- DMA: instruction k = w + 8m covers rows 4k' .. 4k' + 3 of the x (k < NX) or dz (k' = k - NX)
-  // tile; lane L writes row 4k' + L / 16, slot L % 16 = granule ^ swz(row)
-  // per-lane constants of each DMA instruction (g's fields copied to registers first: reading them
-  // inside the loop went through memory and made the compiler wait for every DMA in flight)
-  const u16* const gx = g.x;
-  const u16* const gdz = g.dz;
-  const int XP = g.XP, DP = g.DP;
-  const u16* lbase[PW];
-  int lrow[PW], lpitch[PW], ladj[PW], llim[PW], kslot[PW];
-  bool isx[PW];
-#pragma unroll
-  for (int m = 0; m < PW; ++m) {
-    const int k = min(w + 8 * m, NI - 1);
-    isx[m] = k < NX;
-    kslot[m] = k;
-    lrow[m] = 4 * (isx[m] ? k : k - NX) + (lane >> 4);
-    const int gsrc = ((lane & 15) ^ ((lrow[m] & 7) << 1)) * 8;   // source channel offset of the granule
-    lbase[m] = isx[m] ? gx + ci0 + gsrc : gdz + co0 + gsrc;
-    lpitch[m] = isx[m] ? XP : DP;
-    ladj[m] = isx[m] ? -1 : 0;
-    llim[m] = isx[m] ? XR : SEG;
-  }
-  int lastx = 0, lasty = 0, lastb = 0;
-  auto issue = [&](int st) {
-    // the cursor's segment, or (past the end) the last one again into a stage that is never read
-    const bool have = ileft > 0;
-    const int xs = have ? cx : lastx, y = have ? cy : lasty, b = have ? cb : lastb;
-    lastx = xs; lasty = y; lastb = b;
-    const int x0 = xs * SEG;
-    const int xrow0 = (b * H + y + dy - 1) * W, drow0 = (b * H + y) * W;
-    unsigned char* base = lds + st * STB;
-#pragma unroll
-    for (int m = 0; m < PW; ++m) {
-      const int xc = x0 + lrow[m] + ladj[m];
-      const bool ok = lrow[m] < llim[m] && xc >= 0 && xc < W;
-      const int row = (isx[m] ? xrow0 : drow0) + xc;
-      const u16* src = ok ? lbase[m] + (size_t)row * lpitch[m] : (const u16*)g_zero_row;
-      glds16(src, base + kslot[m] * 1024);
-    }
-    if (have) {
-      advance();
-      skip_invalid();
-    }
-  };
-
-  // ---- operand addresses: transposed reads of rows r0 (+16) (+dx), r0 = 32 ks + 4 (lane >> 4) + (lane & 15) / 4,
-  // 4 channels 4 (lane & 3) of a 16-column block; granule ((c >> 3) ^ swz(row)), byte 8 (lane & 1) in it
-  const int g4 = lane >> 4, qq = (lane & 15) >> 2, pp = lane & 3, rowoff = 4 * g4 + qq;
-  int aoff[3][NWI], boff[NWJ];
-#pragma unroll
-  for (int dx = 0; dx < 3; ++dx) {
-    const int sw = ((rowoff + dx) & 7) << 1;
-#pragma unroll
-    for (int i = 0; i < NWI; ++i) {
-      const int gr = ((wci * 32 + i * 16) >> 3) + (pp >> 1);
-      aoff[dx][i] = (rowoff + dx) * RB + ((gr ^ sw) << 4) + 8 * (pp & 1);
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < NWJ; ++j) {
-    const int gr = ((wco * 64 + j * 16) >> 3) + (pp >> 1);
-    boff[j] = XB + rowoff * RB + ((gr ^ ((rowoff & 7) << 1)) << 4) + 8 * (pp & 1);
-  }
-
-  f32x4 acc[3][NWI][NWJ];
-#pragma unroll
-  for (int t = 0; t < 3; ++t)
-#pragma unroll
-    for (int i = 0; i < NWI; ++i)
-#pragma unroll
-      for (int j = 0; j < NWJ; ++j) acc[t][i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  if (nvalid > 0) {
-    skip_invalid();
-#pragma unroll
-    for (int st = 0; st < WS_ST - 1; ++st) issue(st);
-    int st = 0;
-    const unsigned lds0 = (unsigned)(size_t)((__attribute__((address_space(3))) unsigned char*)lds);
-    if constexpr (PIPE) {
-      // pipelined form: the 20 transposed reads of the next K sub-step (this segment's second, or the next
-      // segment's first) are issued before the 24 MFMAs of this one, whose fragments were read before
-      // the previous sub-step's MFMAs. The next segment's stage must then be published one segment
-      // earlier: each segment retires its own AND the next stage (vmcnt(PW): only the stage issued last
-      // segment stays in flight). The refill after the barrier overwrites the stage of segment k - 1,
-      // last read during segment k - 1. At the last segment the reads of "segment nvalid" hit LDS that
-      // is never used.
-#define WS1_READ(AV, BV, sbase, ks)                                                                         \
-      {                                                                                                     \
-        _Pragma("unroll") for (int j = 0; j < NWJ; ++j) {                                                   \
-          const unsigned pb = (sbase) + boff[j] + 32 * (ks) * RB;                                           \
-          s16x4 v[2] = {tr_read_asm(pb), tr_read_asm(pb + 16 * RB)};                                        \
-          BV[j] = *(bf16x8*)v;                                                                              \
-        }                                                                                                   \
-        _Pragma("unroll") for (int dx = 0; dx < 3; ++dx)                                                    \
-          _Pragma("unroll") for (int i = 0; i < NWI; ++i) {                                                 \
-            const unsigned pa = (sbase) + aoff[dx][i] + 32 * (ks) * RB;                                     \
-            s16x4 v[2] = {tr_read_asm(pa), tr_read_asm(pa + 16 * RB)};                                      \
-            AV[dx][i] = *(bf16x8*)v;                                                                        \
-          }                                                                                                 \
-      }
-#define WS1_MMA(AV, BV, WAIT)                                                                               \
-      {                                                                                                     \
-        asm volatile(WAIT : "+v"(BV[0]), "+v"(BV[1]), "+v"(BV[2]), "+v"(BV[3]), "+v"(AV[0][0]),              \
-                     "+v"(AV[0][1]), "+v"(AV[1][0]), "+v"(AV[1][1]), "+v"(AV[2][0]), "+v"(AV[2][1]));        \
-        _Pragma("unroll") for (int dx = 0; dx < 3; ++dx)                                                    \
-          _Pragma("unroll") for (int i = 0; i < NWI; ++i)                                                   \
-            _Pragma("unroll") for (int j = 0; j < NWJ; ++j)                                                 \
-              acc[dx][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(AV[dx][i], BV[j], acc[dx][i][j], 0, 0, 0); \
-      }
-      // one segment: publish, refill, then its SEG / 32 sub-steps (FC: this sub-step's fragments)
-#define WS1_SEG(FCA, FCB, FNA, FNB)                                                                         \
-      {                                                                                                     \
-        asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(PW) : "memory");                             \
-        issue(st == 0 ? WS_ST - 1 : st - 1);                                                                \
-        const unsigned base = lds0 + st * STB;                                                              \
-        const unsigned nbase = lds0 + (st == WS_ST - 1 ? 0 : st + 1) * STB;                                 \
-        if constexpr (SEG == 64) {                                                                          \
-          WS1_READ(FNA, FNB, base, 1)                                                                       \
-          WS1_MMA(FCA, FCB, "s_waitcnt lgkmcnt(15)")                                                        \
-          WS1_READ(FCA, FCB, nbase, 0)                                                                      \
-          WS1_MMA(FNA, FNB, "s_waitcnt lgkmcnt(15)")                                                        \
-        } else {                                                                                            \
-          WS1_READ(FNA, FNB, nbase, 0)                                                                      \
-          WS1_MMA(FCA, FCB, "s_waitcnt lgkmcnt(15)")                                                        \
-        }                                                                                                   \
-        st = st == WS_ST - 1 ? 0 : st + 1;                                                                  \
-      }
-      static_assert(NWI == 2 && NWJ == 4 && (SEG == 64 || SEG == 32), "operand tie list");
-      bf16x8 a0[3][NWI], b0[NWJ], a1[3][NWI], b1[NWJ];
-      asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(PW) : "memory");   // stages 0 and 1
-      WS1_READ(a0, b0, lds0, 0)
-      int k = 0;
-      if constexpr (SEG == 64) {
-        for (; k < nvalid; ++k) WS1_SEG(a0, b0, a1, b1)
-      } else {
-        for (; k + 1 < nvalid; k += 2) {
-          WS1_SEG(a0, b0, a1, b1)
-          WS1_SEG(a1, b1, a0, b0)
-        }
-        if (k < nvalid) WS1_SEG(a0, b0, a1, b1)
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#undef WS1_SEG
-#undef WS1_MMA
-#undef WS1_READ
-    } else {
-    for (int k = 0; k < nvalid; ++k) {
-        // retire this segment's DMAs (the WS_ST - 2 younger segments stay in flight), then publish
-        asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"((WS_ST - 2) * PW) : "memory");
-        // refill the stage computed last iteration (every wave has passed this barrier after reading it)
-        issue(st == 0 ? WS_ST - 1 : st - 1);
-        const unsigned base = lds0 + st * STB;
-  #pragma unroll
-        for (int ks = 0; ks < SEG / 32; ++ks) {
-          // operand reads as inline asm: the compiler cannot tell the transposed-read intrinsic apart
-          // from the DMA-written stages in flight and put a vmcnt(0) (every DMA, the look-ahead too)
-          // before it. The asm wait below ties the fragments, so no MFMA is scheduled above it.
-          bf16x8 bv[NWJ], av[3][NWI];
-  #pragma unroll
-          for (int j = 0; j < NWJ; ++j) {
-            const unsigned pb = base + boff[j] + 32 * ks * RB;
-            s16x4 v[2] = {tr_read_asm(pb), tr_read_asm(pb + 16 * RB)};
-            bv[j] = *(bf16x8*)v;
-          }
-  #pragma unroll
-          for (int dx = 0; dx < 3; ++dx)
-  #pragma unroll
-            for (int i = 0; i < NWI; ++i) {
-              const unsigned pa = base + aoff[dx][i] + 32 * ks * RB;
-              s16x4 v[2] = {tr_read_asm(pa), tr_read_asm(pa + 16 * RB)};
-              av[dx][i] = *(bf16x8*)v;
-            }
-          static_assert(NWI == 2 && NWJ == 4, "operand tie list");
-          asm volatile("s_waitcnt lgkmcnt(0)"
-                       : "+v"(bv[0]), "+v"(bv[1]), "+v"(bv[2]), "+v"(bv[3]), "+v"(av[0][0]), "+v"(av[0][1]),
-                         "+v"(av[1][0]), "+v"(av[1][1]), "+v"(av[2][0]), "+v"(av[2][1]));
-  #pragma unroll
-          for (int dx = 0; dx < 3; ++dx)
-  #pragma unroll
-            for (int i = 0; i < NWI; ++i)
-  #pragma unroll
-              for (int j = 0; j < NWJ; ++j)
-                acc[dx][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[dx][i], bv[j], acc[dx][i][j], 0, 0, 0);
-        }
-        st = st == WS_ST - 1 ? 0 : st + 1;
-      }
-    }
-    // drain the look-ahead DMAs before the block exits
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
-#pragma unroll
-  for (int dx = 0; dx < 3; ++dx) {
-    float* out = g.part + ((size_t)chunk * 9 + dy * 3 + dx) * g.CI * g.CO;
-#pragma unroll
-    for (int i = 0; i < NWI; ++i)
-#pragma unroll
-      for (int j = 0; j < NWJ; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int ci = ci0 + wci * 32 + i * 16 + 4 * g4 + r, co = co0 + wco * 64 + j * 16 + (lane & 15);
-          out[(size_t)ci * g.CO + co] = acc[dx][i][j][r];
-        }
-  }
-}
-
 // ------------------------------------------------------------------ 3x3 stride-1 weight gradient, column walk, 9 taps
 // k_wgrad_s1c: the S1 weight gradient with ONE block per (SEG-pixel column strip, 64 ci x 128 co tile, run of
 // image rows) accumulating all 9 taps, walking the strip DOWN the image. An x row r (pixels x0 - 1 .. x0 + SEG)
 // is staged once and serves output rows r + 1, r, r - 1 (dy = 0, 1, 2) at its three column shifts (dx); the dz
 // row y once for all 9 taps. Per output row the block stages one x row (SEG + 2 px x 128 B) and one dz row (SEG
-// px x 256 B) for 9 x 64 x 128 MACs per pixel: 2.6 KB of LDS-DMA per MFLOP against k_wgrad_s1's 5.2 (3 taps of
-// one kernel row per staged tile) — the S1 weight gradient is bound by its per-CU staging.
+// px x 256 B) for 9 x 64 x 128 MACs per pixel: 2.6 KB of LDS-DMA per MFLOP. Its predecessor (k_wgrad_s1, r03-r05:
+// row segments, the 3 taps of one kernel row per staged tile) staged 5.2 and measured 1.00 against 0.88 ms per
+// 3-class step (profiles/r06_s1wg_ab.txt); it was unreachable by shape since r06 and has been removed — the S1
+// weight gradient is bound by its per-CU staging.
 // Steps walk the x rows r = -1 .. H of each image (zero rows at -1 and H, so no row ever mixes two images); the
 // step of x row r computes output row r - 1 (none for r < 1). A run of steps [s0, s1) is preceded by its two
 // warm-up rows s0 - 2, s0 - 1 (staged, not computed). Ring: XS = L + 3 x-row slots (three read per step, L in
@@ -2190,6 +1769,13 @@ __global__ __launch_bounds__(WSB, 1) void k_wgrad_s1(WG g, int nseg_x, int seg_p
 // pair per 32 lanes) hits 32 distinct 8-byte bank words. 8 waves = 4 (16 ci) x 2 (64 co), each 9 taps x 4
 // accumulator tiles (144 VGPRs), two waves per SIMD. Partial sums go to part[run][strip][t][ci][co] (the
 // k_wgrad_reduce slab layout: chunks = runs x strips).
+// ds_read_b64_tr_b16 at an LDS byte address, as inline asm (the caller waits on lgkmcnt)
+__device__ __forceinline__ s16x4 tr_read_asm(unsigned addr) {
+  s16x4 r;
+  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r) : "v"(addr));
+  return r;
+}
+constexpr int WSB = 512;    // threads
 constexpr int WC_L = 2;     // steps of DMA look-ahead
 template <int SEG>
 struct S1C {
@@ -2200,7 +1786,7 @@ struct S1C {
 };
 __device__ __forceinline__ int s1c_xswz(int p) { return ((p >> 1) & 3) << 1; }
 __device__ __forceinline__ int s1c_dswz(int p) { return (p & 7) << 1; }
-template <int SEG, int DBG = 0>   // DBG: timing arms (knob 7) — 1: no slab stores, 2: no MFMAs, 4: no LDS reads
+template <int SEG, int DUMMY = 0>
 __global__ __launch_bounds__(WSB, 1) void k_wgrad_s1c(WG g, int nstrip, int steps_per) {
   using K = S1C<SEG>;
   constexpr int PW = K::PW, NXI = K::NXI, NI = K::NI, XR = K::XR;
@@ -2271,7 +1857,9 @@ __global__ __launch_bounds__(WSB, 1) void k_wgrad_s1c(WG g, int nstrip, int step
     for (int m = 0; m < PW; ++m) issue_one(q, m);
   };
 
-  // ---- operand offsets (as k_wgrad_s1): lane reads pixel rowoff (+16) of a 32-pixel K-step, 4 channels 4 (lane & 3)
+  // ---- operand offsets of the transposed reads (ds_read_b64_tr_b16): the lane reads pixels rowoff and rowoff + 16
+  // of a 32-pixel K-step, rowoff = 4 (lane >> 4) + (lane & 15) / 4, at the 4 channels 4 (lane & 3) .. + 3 of a
+  // 16-channel block: granule (channel >> 3) ^ swizzle(pixel) of the pixel's row, byte 8 (lane & 1) in it
   const int g4 = lane >> 4, qq = (lane & 15) >> 2, pp = lane & 3, rowoff = 4 * g4 + qq;
   unsigned aoff[3], boff[4];
 #pragma unroll
@@ -2300,12 +1888,12 @@ __global__ __launch_bounds__(WSB, 1) void k_wgrad_s1c(WG g, int nstrip, int step
       asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"((WC_L - 1) * PW) : "memory");
       const int r = s - (s / HP) * HP - 1;   // (s >= s0 - 2 >= -2; only s >= s0 computes)
       // a computing step spreads the DMA of step s + L over its MFMA groups (issued between them, each piece's
-      // issue cost lies under the wave's MFMAs instead of delaying its first operand reads); DBG 8: all at once.
+      // issue cost lies under the wave's MFMAs instead of delaying its first operand reads).
       // (Written as two ifs, not an early `continue`: with the continue the compiler kept the DMA state live
       // across both paths and spilled the accumulators.)
       const Iss iq = issue_prep(s + WC_L);
       const bool comp = s >= s0 && r >= 1;
-      if (!comp || (DBG & 8)) {
+      if (!comp) {
 #pragma unroll
         for (int m = 0; m < PW; ++m) issue_one(iq, m);
       }
@@ -2319,13 +1907,13 @@ __global__ __launch_bounds__(WSB, 1) void k_wgrad_s1c(WG g, int nstrip, int step
       // kernel row (or the next K-step's dz and first row) are issued before this row's 12 MFMAs, so each
       // wave's LDS reads lie under its own MFMAs (two fragment buffers per operand)
 #define S1C_RB(BV, ks)                                                                                      \
-      if (!(DBG & 4)) _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                        \
+      _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                       \
         const unsigned pb = db + boff[j] + 32 * (ks) * 256;                                                 \
         s16x4 v[2] = {tr_read_asm(pb), tr_read_asm(pb + 16 * 256)};                                         \
         BV[j] = *(bf16x8*)v;                                                                                \
       }
 #define S1C_RA(AV, ks, dy)                                                                                  \
-      if (!(DBG & 4)) _Pragma("unroll") for (int dx = 0; dx < 3; ++dx) {                                     \
+      _Pragma("unroll") for (int dx = 0; dx < 3; ++dx) {                                                    \
         const unsigned pa = xb[dy] + aoff[dx] + 32 * (ks) * 128;                                            \
         s16x4 v[2] = {tr_read_asm(pa), tr_read_asm(pa + 16 * 128)};                                         \
         AV[dx] = *(bf16x8*)v;                                                                               \
@@ -2335,12 +1923,12 @@ __global__ __launch_bounds__(WSB, 1) void k_wgrad_s1c(WG g, int nstrip, int step
       asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(AV[0]), "+v"(AV[1]), "+v"(AV[2]), "+v"(BV[0]), "+v"(BV[1]), \
                    "+v"(BV[2]), "+v"(BV[3]));
 #define S1C_MMA(AV, BV, dy)                                                                                 \
-      if (!(DBG & 2)) _Pragma("unroll") for (int dx = 0; dx < 3; ++dx)                                       \
+      _Pragma("unroll") for (int dx = 0; dx < 3; ++dx)                                                      \
         _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                       \
           acc[(dy) * 3 + dx][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(AV[dx], BV[j], acc[(dy) * 3 + dx][j], 0, 0, 0);
       constexpr int NG = 3 * (SEG / 32);   // MFMA groups per step
 #define S1C_ISSUE(gi)                                                                                       \
-      if (!(DBG & 8)) _Pragma("unroll") for (int m = (gi) * PW / NG; m < ((gi) + 1) * PW / NG; ++m) issue_one(iq, m);
+      _Pragma("unroll") for (int m = (gi) * PW / NG; m < ((gi) + 1) * PW / NG; ++m) issue_one(iq, m);
       // dz fragments double-buffered: the next K-step's dz and first x row are read before this K-step's last
       // MFMA group
       bf16x8 b0[4], b1[4], a0[3], a1[3];
@@ -2384,15 +1972,6 @@ __global__ __launch_bounds__(WSB, 1) void k_wgrad_s1c(WG g, int nstrip, int step
   // lane (a15 = lane & 15, g4) of tile (t, j) holds dW[t][ci0 + 16 wci + 4 g4 + r][co0 + 64 wco + 16 j + a15]
   const size_t slab = (size_t)g.CI * g.CO;
   float* out = g.part + (size_t)(run * nstrip + strip) * 9 * slab;
-  if (DBG & 1) {
-    float t = 0.f;
-#pragma unroll
-    for (int k = 0; k < 9; ++k)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) t += acc[k][j][0] + acc[k][j][1] + acc[k][j][2] + acc[k][j][3];
-    if (t == 12345.f) out[tid] = t;
-    return;
-  }
 #pragma unroll
   for (int t = 0; t < 9; ++t)
 #pragma unroll
@@ -2722,60 +2301,81 @@ static unsigned ew_blocks(long long m, int c) {
   return (unsigned)(b < 1 ? 1 : (b > 65535 ? 65535 : b));
 }
 
-// tuning knobs (rpc_dense_tune): 0 = S1 kernel for 128-multiple outputs (0: by shape, 1: k_conv3x3,
-// 2: k_conv3x3w). By shape: k_conv3x3w (one 128-channel block per CU) when its blocks fill whole rounds
-// of the CUs to >= 90 % (SECOND's 100x88 layers: 504 blocks = 0.98 of 2 rounds), else k_conv3x3 (two
-// 64-channel blocks per CU overlap each other's prologue / epilogue; the 200x176 layers' 858 tiles are
-// 0.84 of 4 rounds for either kernel, and there the register-staged kernel measured 3-8 % faster).
+// ---- tuning knobs (rpc_dense_tune; an environment variable sets one for a whole run)
 static int env_int(const char* name, int dflt) {
   const char* v = getenv(name);
   return v && *v ? atoi(v) : dflt;
 }
+// knob 0 / RPC_DENSE_S1: the S1 kernel for 128-multiple outputs — 0: by shape (s1_select), 1: k_conv3x3,
+// 2: k_conv3x3w, 3: k_conv3x3x, 4: k_conv3x3y
+static int g_s1_variant = env_int("RPC_DENSE_S1", 0);
+// knob 1 / RPC_DENSE_WGRAD: the S1 weight gradient — 0: by shape (k_wgrad_s1c where ci % 64 == 0 and
+// co % 128 == 0, else the per-tap k_wgrad), 1: k_wgrad, 3: k_wgrad_s1c (where it applies). Values 2 and 4 selected
+// the row-segment kernel k_wgrad_s1 (the r03-r05 default; r06: k_wgrad_s1c 0.88 vs k_wgrad_s1 1.00 ms per 3-class
+// step, tools/s1wg_bench.py, profiles/r06_s1wg_ab.txt), which was removed: any other value leaves the knob as it is
+static bool wgrad_variant_ok(int v) { return v == 0 || v == 1 || v == 3; }
+static int env_wgrad_variant() {
+  const int v = env_int("RPC_DENSE_WGRAD", 0);
+  return wgrad_variant_ok(v) ? v : 0;
+}
+static int g_wgrad_variant = env_wgrad_variant();
+// knob 2: the implicit-GEMM grid — 0: by shape (flat for 2 channel blocks), 1: 2-D
+static int g_ig_order = 0;
+// knob 5 / RPC_DENSE_S1N32: k_conv3x3 at 32 output channels per block — 0: by shape (when the 64-channel grid is
+// less than one round of its two blocks per CU), 1: never, 2: always
+static int g_s1_n32 = env_int("RPC_DENSE_S1N32", 0);
+// knob 6 / RPC_DENSE_S1C_SEG: k_wgrad_s1c segment length — 0: by shape, else 32 / 64 / 96
+static int g_s1c_seg = env_int("RPC_DENSE_S1C_SEG", 0);
+// knob 8 / RPC_DENSE_YSPLIT: k_conv3x3y split tail (C3::ysplit) — 1: on, 0: off
+static int g_y_split = env_int("RPC_DENSE_YSPLIT", 1);
 // knob 9 / RPC_DENSE_EW: the row mapping of the BatchNorm elementwise passes — 0: each block one contiguous chunk
 // of rows, all in flight at once (k_bn_apply 4 rows per thread, V = 1; k_bnbwd_apply 8, V = 2; default), 1: the
 // former grid-stride batches (V = 0). Same bits either way (tools/ew_bench.py, profiles/r06_ew_rows_ab.txt:
 // 200x176x6 x 128 bn_apply 17.9 -> 16.8 us, bnbwd_apply 27.2 -> 25.8 us)
 static int g_ew_var = env_int("RPC_DENSE_EW", 0);
-static int g_s1_variant = env_int("RPC_DENSE_S1", 0);   // A/B: RPC_DENSE_S1=<knob 0 value> for a whole run
-// S1 weight gradient (knob 1 / RPC_DENSE_WGRAD): 0 = by shape (k_wgrad_s1c where ci % 64 == 0 and co % 128 == 0,
-// else k_wgrad_s1 for 128-multiples, else k_wgrad), 1 = k_wgrad, 2 = k_wgrad_s1 without its read pipeline,
-// 3 = k_wgrad_s1c, 4 = k_wgrad_s1 (r03-r05 default). r06: k_wgrad_s1c 0.88 vs k_wgrad_s1 1.00 ms per 3-class step
-// (tools/s1wg_bench.py, profiles/r06_s1wg_ab.txt)
-static int g_wgrad_variant = env_int("RPC_DENSE_WGRAD", 0);
-static int g_s1x_dbg = 0;          // knob 4: k_conv3x3x timing experiments (0 = the real kernel)
-static int g_y_split = env_int("RPC_DENSE_YSPLIT", 1);
-static int g_y_zpf = env_int("RPC_DENSE_YZPF", 1);   // knob 10: k_conv3x3y<0, true> for fused BN-backward data gradients   // knob 8: k_conv3x3y split tail (C3::ysplit), 0 = off
-static int g_ig_order = 0;        // implicit-GEMM grid: 0 = by shape (flat for 2 channel blocks), 1 = 2-D   // S1 weight gradient: 0 = k_wgrad_s1 (128-multiple channels), 1 = k_wgrad
+// knob 10 / RPC_DENSE_YZPF: k_conv3x3y<0, true> for fused BN-backward data gradients — 1: on, 0: off
+static int g_y_zpf = env_int("RPC_DENSE_YZPF", 1);
+// (knobs 4 and 7 drove timing arms of k_conv3x3x / y and k_wgrad_s1c that were removed: RPC_ERR_ARG)
 
-// 128-multiple outputs, by shape: k_conv3x3y (two 4-wave 16x16 blocks per CU) when its grid is more than
-// one round of the 2 x CUs block slots (SECOND's 200x176 layers: 858 / 1716 blocks; 128->128 73.6 -> 68.4,
-// 128->256 130.0 -> 114.0 us vs k_conv3x3x), else k_conv3x3x (16x32 tiles, one 8-wave block per CU:
-// 100x88 256->256, 504 16x16 blocks = 0.98 rounds: 59.8 -> 57.6 us) — profiles/r03_conv_bench_y1.log
-static bool s1_ybig(const int* r_img, int cout) {
-  const long long blocks = (long long)r_img[0] * ((r_img[1] + CT - 1) / CT) * ((r_img[2] + CT - 1) / CT) * (cout / 128);
-  return blocks > 2LL * cu_count();
+// ---- S1 kernel selection: the one place that decides which kernel an S1 call runs. The launcher, the fused
+// BatchNorm-backward entry and the two queries (rpc_dense_conv_s1_kernel, rpc_dense_conv_part_rows) all ask it.
+// The values are what rpc_dense_conv_s1_kernel returns.
+enum S1Kernel {
+  S1_K = 0,   // k_conv3x3: 16x16 pixels x 64 (or 32, s1_n32) channels, register-staged, two blocks per CU
+  S1_W = 1,   // k_conv3x3w: 16x16 x 128 channels, LDS-DMA, 8 waves
+  S1_X = 2,   // k_conv3x3x: 16x32 x 128 channels, LDS-DMA, 8 waves, one block per CU (part rows per 16x32 tile)
+  S1_Y = 3,   // k_conv3x3y: 16x16 x 128 channels, LDS-DMA, 4 waves, two blocks per CU
+};
+static long long s1_tiles(const int* r_img, int tw) {   // 16 x tw pixel tiles of the image
+  return (long long)r_img[0] * ((r_img[1] + CT - 1) / CT) * ((r_img[2] + tw - 1) / tw);
 }
-static bool s1_ytwo(const int* r_img, int cout) {
-  return cout % 128 == 0 && (g_s1_variant == 4 || (g_s1_variant == 0 && s1_ybig(r_img, cout)));
+// fits32: the image and the weights are below 2 GB (k_conv3x3x / y address them with 32-bit buffer offsets).
+// k_conv3x3y is not chosen without it; k_conv3x3x still is, and the launcher then answers RPC_ERR_UNSUPPORTED
+// (its part rows are those of 16x32 tiles, which no other kernel writes). The queries pass true, as they always
+// ignored the limit: for an image or weights of 2 GB and above the launcher may run another kernel than they name
+// (w or k_conv3x3 where they say y under knob 0 = 4) or answer RPC_ERR_UNSUPPORTED (where x is chosen).
+static S1Kernel s1_select(const int* r_img, int cout, bool fits32) {
+  if (cout % 128) return S1_K;   // (any multiple of 64)
+  const long long cus = cu_count(), nb = cout / 128;
+  const long long by = s1_tiles(r_img, CT) * nb, bx = s1_tiles(r_img, XTW) * nb;   // blocks of y / w, of x
+  // y when its grid is more than one round of the 2 x CUs block slots (SECOND's 200x176 layers: 858 / 1716 blocks;
+  // 128->128 73.6 -> 68.4, 128->256 130.0 -> 114.0 us vs k_conv3x3x), else x (one 8-wave block per CU: 100x88
+  // 256->256, 504 16x16 blocks = 0.98 rounds: 59.8 -> 57.6 us) — profiles/r03_conv_bench_y1.log
+  if (fits32 && (g_s1_variant == 4 || (g_s1_variant == 0 && by > 2 * cus))) return S1_Y;
+  // ... unless x's grid is at most half a round of its one-block-per-CU slots, which leaves most CUs idle
+  // (CenterPoint's 128x128 / 64x64 images at batch 4 and 128 channels: 128 / 32 blocks). Those go to the 16x16-tile
+  // kernels below with 2x / 4x the blocks: 4 x 128 x 128 to k_conv3x3w (256 blocks, one whole round), 4 x 64 x 64 to
+  // k_conv3x3 (measured with every S1 launch on k_conv3x3, knob 0 = 1: CenterPoint 164.8 / 164.9 -> 166.5 / 166.4
+  // frames/s, profiles/r04_ab_centerpoint_s1.txt; the metric's SECOND shapes keep x / y: their smallest grid is
+  // 252 blocks)
+  if (g_s1_variant == 3 || (g_s1_variant == 0 && 2 * bx > cus)) return S1_X;
+  // w (one 128-channel block per CU) when its blocks fill whole rounds of the CUs to >= 90 %, else k_conv3x3
+  // (two 64-channel blocks per CU overlap each other's prologue / epilogue)
+  if (g_s1_variant == 1) return S1_K;
+  if (g_s1_variant == 2) return S1_W;
+  const long long rounds = (by + cus - 1) / cus;
+  return by * 10 >= rounds * cus * 9 ? S1_W : S1_K;
 }
-// grids of at most half a round of the x kernel's one-block-per-CU slots (CenterPoint's 128x128 / 64x64 images at
-// batch 4: 128 / 64 blocks) leave most CUs idle; there the 64-channel k_conv3x3 (two 4-wave blocks per CU, 4x
-// the blocks) is used (CenterPoint 164.8 / 164.9 -> 166.5 / 166.4 frames/s with every S1 launch on it,
-// profiles/r04_ab_centerpoint_s1.txt; the metric's SECOND shapes keep x / y: their smallest grid is 252 blocks)
-static bool s1_small(const int* r_img, int cout) {
-  const long long bx = (long long)r_img[0] * ((r_img[1] + CT - 1) / CT) * ((r_img[2] + XTW - 1) / XTW) * (cout / 128);
-  return 2 * bx <= cu_count();
-}
-static bool s1_xwide(const int* r_img, int cout) {
-  return cout % 128 == 0 && (g_s1_variant == 3 || (g_s1_variant == 0 && !s1_small(r_img, cout)));
-}
-
-// k_conv3x3 at 32 output channels per block when the 64-channel grid is less than one round of its two
-// blocks per CU (knob 5 / RPC_DENSE_S1N32: 0 = by shape, 1 = never, 2 = always)
-static int g_s1_n32 = env_int("RPC_DENSE_S1N32", 0);
-// k_wgrad_s1c segment length (knob 6 / RPC_DENSE_S1C_SEG: 0 = by shape, else 32 / 64 / 96)
-static int g_s1c_seg = env_int("RPC_DENSE_S1C_SEG", 0);
-static int g_s1c_dbg = 0;   // knob 7: k_wgrad_s1c timing arms (0 = the real kernel)
 
 // k_wgrad_s1c geometry: column strips of SEG pixels (the segment length with the least padding of an image row),
 // tiles of 64 ci x 128 co, runs of steps sized so strips x tiles x runs fills one round of the CUs (one block per
@@ -2813,66 +2413,24 @@ static bool s1_n32(int tiles, int cout) {
   return (long long)tiles * (cout / 64) < 2LL * cu_count();
 }
 
-static bool s1_wide(int tiles, int cout) {
-  if (cout % 128 || g_s1_variant == 1) return false;
-  if (g_s1_variant == 2) return true;
-  const long long items = (long long)tiles * (cout / 128), cus = cu_count();
-  const long long rounds = (items + cus - 1) / cus;
-  return items * 10 >= rounds * cus * 9;
-}
-
 extern "C" int rpc_dense_tune(int knob, int value) {
-  if (knob == 0) {
-    const int old = g_s1_variant;
-    if (value >= 0) g_s1_variant = value;
-    return old;
+  int* g;
+  bool ok = value >= 0;   // a value out of a knob's range (any negative one) only reads it
+  const bool flag = value == 0 || value == 1;
+  switch (knob) {
+    case 0: g = &g_s1_variant; break;
+    case 1: g = &g_wgrad_variant; ok = wgrad_variant_ok(value); break;
+    case 2: g = &g_ig_order; break;
+    case 5: g = &g_s1_n32; ok = value >= 0 && value <= 2; break;
+    case 6: g = &g_s1c_seg; break;
+    case 8: g = &g_y_split; ok = flag; break;
+    case 9: g = &g_ew_var; ok = flag; break;
+    case 10: g = &g_y_zpf; ok = flag; break;
+    default: return RPC_ERR_ARG;
   }
-  if (knob == 1) {
-    const int old = g_wgrad_variant;
-    if (value >= 0) g_wgrad_variant = value;
-    return old;
-  }
-  if (knob == 4) {
-    const int old = g_s1x_dbg;
-    if (value >= 0 && value <= 255) g_s1x_dbg = value;
-    return old;
-  }
-  if (knob == 5) {
-    const int old = g_s1_n32;
-    if (value >= 0 && value <= 2) g_s1_n32 = value;
-    return old;
-  }
-  if (knob == 7) {
-    const int old = g_s1c_dbg;
-    if (value >= 0) g_s1c_dbg = value;
-    return old;
-  }
-  if (knob == 6) {
-    const int old = g_s1c_seg;
-    if (value >= 0) g_s1c_seg = value;
-    return old;
-  }
-  if (knob == 10) {
-    const int old = g_y_zpf;
-    if (value == 0 || value == 1) g_y_zpf = value;
-    return old;
-  }
-  if (knob == 8) {
-    const int old = g_y_split;
-    if (value == 0 || value == 1) g_y_split = value;
-    return old;
-  }
-  if (knob == 9) {
-    const int old = g_ew_var;
-    if (value == 0 || value == 1) g_ew_var = value;
-    return old;
-  }
-  if (knob == 2) {
-    const int old = g_ig_order;
-    if (value >= 0) g_ig_order = value;
-    return old;
-  }
-  return RPC_ERR_ARG;
+  const int old = *g;
+  if (ok) *g = value;
+  return old;
 }
 
 // the S1 kernels; bnz / bnp (k_conv3x3x / y only, checked by the caller): BatchNorm-backward partial sums
@@ -2883,46 +2441,27 @@ static int launch_s1(const IG& g, const u16* bnz, const float* bnp, hipStream_t 
        bnz, bnp, 0};
   const bool fits32 = (long long)g.M * g.SP * 2 < (1LL << 31) && 9LL * g.COUT * g.CIN * 2 < (1LL << 31);
   const int rimg[3] = {g.R.B, g.R.H, g.R.W};
-  if (s1_ytwo(rimg, g.COUT) && fits32) {
+  const int tiles = g.R.B * TY * TX;
+  const S1Kernel k = s1_select(rimg, g.COUT, fits32);
+  if (k == S1_X && !fits32) return RPC_ERR_UNSUPPORTED;   // (see s1_select)
+  if (bnz != nullptr && k != S1_X && k != S1_Y) return RPC_ERR_UNSUPPORTED;
+  if (k == S1_Y) {
     // the items past the last whole round of one block per CU (k_conv3x3y's time is a staircase in
     // ceil(items / CUs), profiles/r06_conv3x3y_tiles.txt) run as 64-channel halves when those fit one round
-    const int items = g.R.B * TY * TX * (g.COUT / 128), tail = items % cu_count();
-    c.ysplit = (g_y_split && g_s1x_dbg == 0 && items > cu_count() && 2 * tail <= cu_count()) ? tail : 0;
+    const int items = tiles * (g.COUT / 128), tail = items % cu_count();
+    c.ysplit = (g_y_split && items > cu_count() && 2 * tail <= cu_count()) ? tail : 0;
     const dim3 grid(items + c.ysplit);
-    switch (g_s1x_dbg) {
-      case 1: hipLaunchKernelGGL(k_conv3x3y<1>, grid, dim3(YB), 0, st, c); break;
-      case 17: hipLaunchKernelGGL(k_conv3x3y<17>, grid, dim3(YB), 0, st, c); break;
-      case 64: hipLaunchKernelGGL(k_conv3x3y<64>, grid, dim3(YB), 0, st, c); break;
-      case 65: hipLaunchKernelGGL(k_conv3x3y<65>, grid, dim3(YB), 0, st, c); break;
-      case 81: hipLaunchKernelGGL(k_conv3x3y<81>, grid, dim3(YB), 0, st, c); break;
-      case 128: hipLaunchKernelGGL(k_conv3x3y<128>, grid, dim3(YB), 0, st, c); break;
-      default:
-        if (bnz != nullptr && g_y_zpf) hipLaunchKernelGGL((k_conv3x3y<0, true>), grid, dim3(YB), 0, st, c);
-        else hipLaunchKernelGGL(k_conv3x3y<0>, grid, dim3(YB), 0, st, c);
-    }
-  } else if (s1_xwide(rimg, g.COUT)) {
-    if (!fits32) return RPC_ERR_UNSUPPORTED;   // 32-bit buffer offsets (part rows are those of 16x32 tiles)
+    if (bnz != nullptr && g_y_zpf) hipLaunchKernelGGL((k_conv3x3y<0, true>), grid, dim3(YB), 0, st, c);
+    else hipLaunchKernelGGL(k_conv3x3y<0>, grid, dim3(YB), 0, st, c);
+  } else if (k == S1_X) {
     c.TX = (g.R.W + XTW - 1) / XTW;
-    const dim3 grid(g.R.B * TY * c.TX * (g.COUT / 128));
-    switch (g_s1x_dbg) {
-      case 1: hipLaunchKernelGGL(k_conv3x3x<1>, grid, dim3(WB), 0, st, c); break;
-      case 3: hipLaunchKernelGGL(k_conv3x3x<3>, grid, dim3(WB), 0, st, c); break;
-      case 12: hipLaunchKernelGGL(k_conv3x3x<12>, grid, dim3(WB), 0, st, c); break;
-      case 13: hipLaunchKernelGGL(k_conv3x3x<13>, grid, dim3(WB), 0, st, c); break;
-      case 30: hipLaunchKernelGGL(k_conv3x3x<30>, grid, dim3(WB), 0, st, c); break;
-      case 31: hipLaunchKernelGGL(k_conv3x3x<31>, grid, dim3(WB), 0, st, c); break;
-      case 32: hipLaunchKernelGGL(k_conv3x3x<32>, grid, dim3(WB), 0, st, c); break;
-      case 128: hipLaunchKernelGGL(k_conv3x3x<128>, grid, dim3(WB), 0, st, c); break;
-      default: hipLaunchKernelGGL(k_conv3x3x<0>, grid, dim3(WB), 0, st, c);
-    }
-  } else if (bnz != nullptr) {
-    return RPC_ERR_UNSUPPORTED;
-  } else if (s1_wide(g.R.B * TY * TX, g.COUT)) {
-    hipLaunchKernelGGL(k_conv3x3w<0>, dim3(g.R.B * TY * TX * (g.COUT / 128)), dim3(WB), 0, st, c);
-  } else if (s1_n32(g.R.B * TY * TX, g.COUT)) {
-    hipLaunchKernelGGL((k_conv3x3<0, 32>), dim3(g.R.B * TY * TX, g.COUT / 32), dim3(CBLK), 0, st, c);
+    hipLaunchKernelGGL(k_conv3x3x<0>, dim3(g.R.B * TY * c.TX * (g.COUT / 128)), dim3(WB), 0, st, c);
+  } else if (k == S1_W) {
+    hipLaunchKernelGGL(k_conv3x3w<0>, dim3(tiles * (g.COUT / 128)), dim3(WB), 0, st, c);
+  } else if (s1_n32(tiles, g.COUT)) {
+    hipLaunchKernelGGL((k_conv3x3<0, 32>), dim3(tiles, g.COUT / 32), dim3(CBLK), 0, st, c);
   } else {
-    hipLaunchKernelGGL(k_conv3x3<0>, dim3(g.R.B * TY * TX, g.COUT / 64), dim3(CBLK), 0, st, c);
+    hipLaunchKernelGGL(k_conv3x3<0>, dim3(tiles, g.COUT / 64), dim3(CBLK), 0, st, c);
   }
   RPC_LAUNCH_CHECK();
   return RPC_OK;
@@ -2966,7 +2505,7 @@ extern "C" int rpc_dense_conv_bnbwd(const void* src, int sp, int cin, const void
                                     const void* bnz, const float* bnp, float* part, const int* r_img, void* stream) {
   if (!src || !wt || !out || !r_img || !bnz || !bnp || !part) return RPC_ERR_ARG;
   if (cin % BK || cout % 128 || sp < cin || op < cout || (sp & 7) || (op & 7)) return RPC_ERR_ARG;
-  if (!s1_ytwo(r_img, cout) && !s1_xwide(r_img, cout)) return RPC_ERR_UNSUPPORTED;
+  if (s1_select(r_img, cout, true) < S1_X) return RPC_ERR_UNSUPPORTED;   // only x / y have the fused epilogue
   IG g{(const u16*)src, sp, cin, (const u16*)wt, cout, (u16*)out, op, 0, 0, part, img3(r_img), img3(r_img),
        img3(r_img), 0};
   g.M = g.R.B * g.R.H * g.R.W;
@@ -2977,16 +2516,13 @@ extern "C" int rpc_dense_conv_bnbwd(const void* src, int sp, int cin, const void
 
 extern "C" int rpc_dense_conv_s1_kernel(int map, int cout, const int* r_img) {
   if (map != M_S1 || !r_img || cout % 64) return -1;
-  const int TY = (r_img[1] + CT - 1) / CT, TX = (r_img[2] + CT - 1) / CT;
-  if (s1_ytwo(r_img, cout)) return 3;
-  if (s1_xwide(r_img, cout)) return 2;
-  return s1_wide(r_img[0] * TY * TX, cout) ? 1 : 0;
+  return s1_select(r_img, cout, true);
 }
 
 extern "C" int rpc_dense_conv_part_rows(int map, int cout, const int* r_img) {
   if (!r_img || map < M_S1 || map > M_G2) return -1;
-  if (map == M_S1 && !s1_ytwo(r_img, cout) && s1_xwide(r_img, cout))   // one row per 16x32 tile
-    return r_img[0] * ((r_img[1] + CT - 1) / CT) * ((r_img[2] + XTW - 1) / XTW);
+  // k_conv3x3x: one row per 16x32 tile
+  if (map == M_S1 && s1_select(r_img, cout, true) == S1_X) return (int)s1_tiles(r_img, XTW);
   return rpc_dense_conv_blocks(map, r_img);
 }
 
@@ -3029,39 +2565,16 @@ extern "C" int rpc_dense_wgrad(int map, int kind, const void* x, int xp, int ci,
   const int rows_per = ((M + chunks - 1) / chunks + 63) / 64 * 64;
   WG g{(const u16*)x, xp, (const u16*)dz, dp, ci, co, R, S, O, M, rows_per, part};
   int nred = chunks;
-  if (map == M_S1 && s1c_ok(ci, co) && (g_wgrad_variant == 0 || g_wgrad_variant == 3)) {
+  if (map == M_S1 && s1c_ok(ci, co) && g_wgrad_variant != 1) {
     // column walk, all 9 taps per block
     const S1cGeo q = s1c_geometry(R, ci, co);
     nred = q.nrun * q.nstrip;
     if (ws_bytes < (size_t)nred * slab * sizeof(float)) return RPC_ERR_WORKSPACE;
     if ((size_t)M * (xp > dp ? xp : dp) >= (1ULL << 31)) return RPC_ERR_UNSUPPORTED;   // 32-bit lane offsets
     const dim3 grid(q.nrun * q.nstrip * (ci / 64) * (co / 128));
-    if (q.seg == 96) {
-      switch (g_s1c_dbg) {
-        case 1: hipLaunchKernelGGL((k_wgrad_s1c<96, 1>), grid, dim3(WSB), 0, st, g, q.nstrip, q.steps_per); break;
-        case 3: hipLaunchKernelGGL((k_wgrad_s1c<96, 3>), grid, dim3(WSB), 0, st, g, q.nstrip, q.steps_per); break;
-        case 7: hipLaunchKernelGGL((k_wgrad_s1c<96, 7>), grid, dim3(WSB), 0, st, g, q.nstrip, q.steps_per); break;
-        case 5: hipLaunchKernelGGL((k_wgrad_s1c<96, 5>), grid, dim3(WSB), 0, st, g, q.nstrip, q.steps_per); break;
-        case 8: hipLaunchKernelGGL((k_wgrad_s1c<96, 8>), grid, dim3(WSB), 0, st, g, q.nstrip, q.steps_per); break;
-        default: hipLaunchKernelGGL((k_wgrad_s1c<96>), grid, dim3(WSB), 0, st, g, q.nstrip, q.steps_per);
-      }
-    } else if (q.seg == 64) hipLaunchKernelGGL(k_wgrad_s1c<64>, grid, dim3(WSB), 0, st, g, q.nstrip, q.steps_per);
+    if (q.seg == 96) hipLaunchKernelGGL(k_wgrad_s1c<96>, grid, dim3(WSB), 0, st, g, q.nstrip, q.steps_per);
+    else if (q.seg == 64) hipLaunchKernelGGL(k_wgrad_s1c<64>, grid, dim3(WSB), 0, st, g, q.nstrip, q.steps_per);
     else hipLaunchKernelGGL(k_wgrad_s1c<32>, grid, dim3(WSB), 0, st, g, q.nstrip, q.steps_per);
-  } else if (map == M_S1 && ci % 128 == 0 && co % 128 == 0 &&
-             (g_wgrad_variant == 0 || g_wgrad_variant == 2 || g_wgrad_variant == 4)) {
-    // tap-sharing row-segment kernel: segment length with the least padding of the image row
-    const int seg = (R.W + 63) / 64 * 64 <= (R.W + 31) / 32 * 32 ? 64 : 32;
-    const int nsx = (R.W + seg - 1) / seg, nseg = R.B * R.H * nsx;
-    const int seg_per = (nseg + chunks - 1) / chunks;
-    const dim3 grid(chunks * 3 * (ci / 128) * (co / 128));
-    // knob 1 = 2: the former loop (each sub-step's 20 transposed reads, then its 24 MFMAs); the default
-    // issues the next sub-step's reads first (bit-identical; 200x176 128->128 91.3 -> 90.7 us, 100x88
-    // 256->256 94.8 -> 90.9, 128->256 153.4 -> 150.2, profiles/r03_wgrad_pipe.log)
-    const bool pipe = g_wgrad_variant != 2;
-    if (seg == 64 && pipe) hipLaunchKernelGGL((k_wgrad_s1<64, 1>), grid, dim3(WSB), 0, st, g, nsx, seg_per);
-    else if (seg == 64) hipLaunchKernelGGL((k_wgrad_s1<64, 0>), grid, dim3(WSB), 0, st, g, nsx, seg_per);
-    else if (pipe) hipLaunchKernelGGL((k_wgrad_s1<32, 1>), grid, dim3(WSB), 0, st, g, nsx, seg_per);
-    else hipLaunchKernelGGL((k_wgrad_s1<32, 0>), grid, dim3(WSB), 0, st, g, nsx, seg_per);
   } else switch (map) {
     case M_S1: launch_wgrad<M_S1>(g, chunks, st); break;
     case M_S2: launch_wgrad<M_S2>(g, chunks, st); break;

@@ -409,7 +409,7 @@ def test_s1_conv3x3_32_channel_blocks_bitexact(ci, co, B, H, W):
                                          (128, 128, 1, 16, 32), (256, 128, 2, 37, 45), (128, 256, 2, 33, 17),
                                          (128, 128, 3, 24, 40), (128, 256, 1, 9, 130), (384, 128, 1, 21, 70),
                                          (192, 128, 1, 19, 33)])
-@pytest.mark.parametrize("variant", [3, 4, 31, 41])
+@pytest.mark.parametrize("variant", [3, 4])
 def test_s1_wide_tile_kernel(ci, co, B, H, W, variant):
     """k_conv3x3x (16x32-pixel tiles, 32-channel K-steps, rpc_dense_tune knob 0 = 3) and k_conv3x3y (two
     4-wave 16x16 blocks per CU, knob 0 = 4) against float64 torch on
@@ -418,13 +418,8 @@ def test_s1_wide_tile_kernel(ci, co, B, H, W, variant):
     rpc_dense_conv_part_rows rows (later rows untouched), and the output within 1 bf16 ulp of k_conv3x3's
     (same 32-channel MFMA sums, added in another order). Shapes: SECOND's (200x176 with an 8-row last
     tile row and a 16-column last tile column; 100x88), one tile, partial rows / columns, an odd number of
-    32-channel K-steps (192 channels). Variants 31 / 41: knob 4 = 128 against the default loop of
-    k_conv3x3x / k_conv3x3y (x: the quarter-step-ahead fragment reads against the staggered partner
-    groups; y: the former read-then-MFMA loop against the quarter-step-ahead one): the same MFMAs in the
-    same order per accumulator, so bit-identical."""
+    32-channel K-steps (192 channels)."""
     lib = _ffi.load()
-    pipe = variant in (31, 41)
-    variant = variant // 10 if pipe else variant
     x = _rand(B, ci, H, W, seed=31)
     Wt = _rand(co, ci, 3, 3, seed=32, scale=0.05)
     wf, _ = _wprep(Wt, 0, 9, 1)
@@ -432,9 +427,8 @@ def test_s1_wide_tile_kernel(ci, co, B, H, W, variant):
     base = _rand(B, co, H, W, seed=33)
     ref = F.conv2d(x.double(), Wt.double(), padding=1).permute(0, 2, 3, 1).reshape(-1, co)
     outs = {}
-    for v in ((-1, variant, 1) if pipe else (variant, 1)):
-        old = lib.rpc_dense_tune(0, variant if v == -1 else v)
-        old_dbg = lib.rpc_dense_tune(4, 128 if v == -1 else 0)
+    for v in (variant, 1):
+        old = lib.rpc_dense_tune(0, v)
         try:
             if v != 1:
                 assert lib.rpc_dense_conv_s1_kernel(S1, co, _ffi.int_arr(img)) == variant - 1
@@ -445,13 +439,9 @@ def test_s1_wide_tile_kernel(ci, co, B, H, W, variant):
             torch.cuda.synchronize()
         finally:
             lib.rpc_dense_tune(0, old)
-            lib.rpc_dense_tune(4, old_dbg)
         assert 1 <= rows <= part.shape[0]
         assert torch.all(part[rows:] == 0)
         outs[v] = (z, acc, part[:rows].double().sum(0))
-    if pipe:
-        for a, b in zip(outs[-1], outs[variant]):
-            assert torch.equal(a, b)
     z, acc, sp = outs[variant]
     _close_bf16(z, ref)
     _close_bf16(acc, ref + base.permute(0, 2, 3, 1).reshape(-1, co).double())
@@ -580,41 +570,6 @@ def _s1_dgrad_fused_case(lib, ci, co, B, H, W):
         torch.testing.assert_close(a, b_, rtol=1e-5, atol=1e-5 * float(b_.abs().max()) + 1e-7)
 
 
-@pytest.mark.parametrize("ci,co,B,H,W", [(128, 128, 1, 200, 176), (256, 256, 1, 100, 88), (256, 128, 2, 37, 45),
-                                         (128, 128, 2, 17, 70), (128, 256, 1, 5, 130)])
-def test_s1_wgrad_tap_sharing_kernel(ci, co, B, H, W):
-    """k_wgrad_s1 (row segments, 3 taps per staged tile) against float64 torch at 1e-5 of the gradient
-    scale, and against the per-tap kernel k_wgrad (rpc_dense_tune knob 1) — same bf16 products, fp32
-    sums in another order: within 2e-6 of the scale — and k_wgrad_s1's former loop (knob 1 = 2: each sub-step's
-    transposed reads, then its MFMAs) bit-identical to the default one, which issues the next sub-step's
-    reads before this one's MFMAs."""
-    lib = _ffi.load()
-    x = _rand(B, ci, H, W, seed=31)
-    dz = _rand(B, co, H, W, seed=32)
-    Wt = _rand(co, ci, 3, 3, seed=33, scale=0.05)
-    wr = Wt.double().requires_grad_(True)
-    F.conv2d(x.double(), wr, padding=1).backward(dz.double())
-    img = _ffi.int_arr((B, H, W))
-    wsz = lib.rpc_dense_wgrad_workspace_size(S1, img, ci, co)
-    ws = _ffi.workspace(wsz, DEV)
-    xn, dn = _nhwc(x), _nhwc(dz)
-    outs = []
-    for variant in (4, 1, 2):   # (knob 1: 4 = k_wgrad_s1, 1 = k_wgrad, 2 = k_wgrad_s1's former loop)
-        old = lib.rpc_dense_tune(1, variant)
-        try:
-            dW = torch.full(Wt.shape, float("nan"), dtype=torch.float32, device=DEV)
-            _ffi.check(lib.rpc_dense_wgrad(S1, 0, _ffi.ptr(xn), ci, ci, _ffi.ptr(dn), co, co, img, img, img,
-                                           _ffi.ptr(dW), _ffi.ptr(ws), wsz, _ffi.stream_of(dW)), "rpc_dense_wgrad")
-            torch.cuda.synchronize()
-        finally:
-            lib.rpc_dense_tune(1, old)
-        outs.append(dW.double().cpu())
-    scale = wr.grad.abs().max().item()
-    assert (outs[0] - wr.grad).abs().max().item() <= 1e-5 * scale
-    assert (outs[0] - outs[1]).abs().max().item() <= 2e-6 * scale
-    assert torch.equal(outs[0], outs[2])
-
-
 def test_wprep_batch_matches_per_layer_prep():
     """rpc_dense_wprep_batch (LDS-tiled, every layer of a module in one launch) writes the same bf16
     operands as rpc_dense_wprep (per element) for Conv2d 3x3 (flipped and not), ConvTranspose2d k2 / k1
@@ -644,13 +599,17 @@ def test_wprep_batch_matches_per_layer_prep():
 
 
 @pytest.mark.parametrize("ci,co,B,H,W", [(128, 128, 2, 200, 176), (256, 256, 2, 100, 88), (256, 128, 1, 37, 45),
-                                         (64, 128, 2, 17, 70), (192, 256, 1, 5, 130), (128, 128, 3, 1, 33)])
+                                         (64, 128, 2, 17, 70), (192, 256, 1, 5, 130), (128, 128, 3, 1, 33),
+                                         (256, 128, 2, 37, 45), (128, 128, 2, 17, 70), (128, 256, 1, 5, 130),
+                                         (128, 128, 1, 200, 176), (256, 256, 1, 100, 88)])
 def test_s1_wgrad_column_walk_kernel(ci, co, B, H, W):
     """k_wgrad_s1c (rpc_dense_tune knob 1 = 3: column strips walked down the image, all 9 taps per block, one staged
     x row per output row) against float64 torch at 1e-5 of the gradient scale and against the per-tap kernel k_wgrad
     (knob 1 = 1: the same bf16 products, fp32 sums in another order) within 2e-6; run twice, bit-identical; every
     segment length (knob 6: 32, 64, 96 pixels) within 1e-5 of float64. Shapes:
-    the metric's S1 layers at batch 2, 64-channel tiles (ci 64, 192), one-row images, strips past the image edge."""
+    the metric's S1 layers at batch 2, 64-channel tiles (ci 64, 192), one-row images, strips past the image edge, and
+    every shape the removed row-segment kernel k_wgrad_s1 was held to (three small ones, the metric's layers at
+    batch 1)."""
     lib = _ffi.load()
     x = _rand(B, ci, H, W, seed=41)
     dz = _rand(B, co, H, W, seed=42)

@@ -1,6 +1,7 @@
 """S1 weight-gradient timing (rpc_dense_wgrad, its slab reduce included) on the metric's SECOND shapes, per
-rpc_dense_tune knob-1 variant: 4 = k_wgrad_s1 (row segments, 3 taps per block), 3 = k_wgrad_s1c (column walk,
-9 taps per block; the default 0 since r06). HIP-event us per call, median of rounds.
+rpc_dense_tune knob-1 variant: 3 = k_wgrad_s1c (column walk, 9 taps per block; the default 0 since r06), 1 = the
+per-tap k_wgrad. (The row-segment kernel it was first compared with, knob 1 = 4, was removed with the kernel;
+its figures are in profiles/r06_s1wg_ab.txt.) HIP-event us per call, median of rounds.
 
     python tools/s1wg_bench.py [variants...]
 """
@@ -19,7 +20,7 @@ SHAPES = [("200x176 256->128", (6, 200, 176), 256, 128, 1), ("200x176 128->128",
 
 
 def main():
-    variants = sys.argv[1:] or ["4", "3"]   # "v" or "v:seg" or "v:seg:dbg" (knobs 6 / 7: k_wgrad_s1c segment, arms)
+    variants = sys.argv[1:] or ["3", "1"]   # "v" or "v:seg" (knob 6: k_wgrad_s1c segment length)
     lib = _ffi.load()
     dev = torch.device("cuda")
     tot = {v: 0.0 for v in variants}
@@ -34,11 +35,9 @@ def main():
         st = _ffi.stream_of(dW)
         row = []
         for v in variants:
-            kv, _, rest = v.partition(":")
-            seg, _, dbg = rest.partition(":")
+            kv, _, seg = v.partition(":")
             old = lib.rpc_dense_tune(1, int(kv))
             old6 = lib.rpc_dense_tune(6, int(seg or 0))
-            old7 = lib.rpc_dense_tune(7, int(dbg or 0))
 
             def run():
                 _ffi.check(lib.rpc_dense_wgrad(S1, 0, _ffi.ptr(x), ci, ci, _ffi.ptr(dz), co, co, R, R, R, _ffi.ptr(dW),
@@ -46,7 +45,6 @@ def main():
             us = timeit(run)
             lib.rpc_dense_tune(1, old)
             lib.rpc_dense_tune(6, old6)
-            lib.rpc_dense_tune(7, old7)
             tot[v] += us * n
             fl = 2.0 * M * ci * co * 9
             row.append(f"v{v} {us:7.1f} us ({fl / us / 1e6:6.0f} TFLOP/s)")
