@@ -135,6 +135,8 @@ KITTI_MAX_DET = 512   # include/rpc_hip.h RPC_KITTI_MAX_DET
 KITTI_MAX_GT = 128    # RPC_KITTI_MAX_GT
 KITTI_MAX_THR = 41    # RPC_KITTI_MAX_THR
 KITTI_NO_SCORE = -10000000.0   # RPC_KITTI_NO_SCORE
+KITTI_MAX_DC = 64     # RPC_KITTI_MAX_DC
+KITTI_SIM_ONE = float(1 << 40)   # RPC_KITTI_SIM_ONE
 GT_MAX_BOXES = 128    # RPC_GT_MAX_BOXES
 GT_MAX_CAND = 128     # RPC_GT_MAX_CAND
 GT_MAX_TRY = 512      # RPC_GT_MAX_TRY
@@ -281,6 +283,10 @@ SIGNATURES = {
                                      i32, vp, vp]),
     "rpc_kitti_match_counts": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, C.c_longlong, C.c_longlong, vp, i32,
                                      i32, vp, vp, vp, vp]),
+    "rpc_kitti_project": (i32, [vp, C.c_longlong, vp, i32, i32, vp, vp, C.POINTER(C.c_float), vp, vp, vp, vp, vp, vp]),
+    "rpc_kitti_overlaps_2d": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, C.c_longlong, vp, vp]),
+    "rpc_kitti_match_counts_aos": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, C.c_longlong, C.c_longlong, vp,
+                                         i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
     "rpc_nus_match": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.c_longlong, C.c_longlong, i32, vp, i32,
                             vp, vp]),
     "rpc_nus_tp_errors": (i32, [vp, vp, vp, vp, vp, vp, C.c_longlong, C.c_longlong, vp, vp]),
